@@ -11,13 +11,25 @@ Default workload (N=1): BASELINE config 5 shape on one GPU -- 1M hosts x 10k rea
 rank), as in the scenario-batch config: weak scaling, no collective on the data path; only the
 final timing max is reduced. `--shard hosts` splits one round's host dimension instead.
 
-Parity: after the timed steps, rank 0 compares the round it placed (placement, processing
-order, final availability, RNG state) with the CPU restatement (oracle/, itself pinned to the
-reference's golden runs) on the same inputs and prints `"parity": true/false`. The default run
-also times the other four policies at the config-5 size and all five at the config-3 size
-(`extra`), each with its own parity check.
+A plain run does only what the headline figure needs: set up, warm up, time the steps (no
+kernel events), write the outputs if --dump-outputs is given, print the line.
 
-Run:  python bench.py [--gpus N --steps K --warmup W --mode ca_bf --hosts H --tasks T]
+--full adds everything else, each outside the timed steps: the dominant kernel's HIP-event time
+and roofline, the CPU baseline and the parity check -- rank 0 compares the round it placed
+(placement, processing order, final availability, RNG state) with the CPU restatement (oracle/,
+itself pinned to the reference's golden runs) on the same inputs and prints `"parity":
+true/false`. With the default workload --full also times the other four policies at the
+config-5 size and all five at the config-3 size (`extra`), each with its own parity check, and
+replays the recorded simulations; for N > 1 it adds the config-4 scenario line. The options
+that tune those legs (--parity, --extra, --replay, --cpu-baseline-seconds, --c4-batch) act under
+--full only.
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step computed --
+placement, order, final availability (and the RNG state of an opportunistic round) -- as
+DIR/<name>.npy in float64. The inputs are seeded, so two builds run with the same arguments can
+be compared array for array.
+
+Run:  python bench.py [--gpus N --steps K --warmup W --mode ca_bf --hosts H --tasks T] [--full]
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts N rank processes
 itself (before anything touches the GPU); under torchrun WORLD_SIZE must equal N.
 """
@@ -63,6 +75,13 @@ def parse():
     p.add_argument("--epochs", type=int, default=1,
                    help="cost_aware best-fit: 1 walks groups side by side in speculative epochs "
                         "(default), 0: one group after the other")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: kernel events and the "
+                        "roofline, the CPU baseline, parity against the oracle, the extra "
+                        "workloads, the replays and (N > 1) the config-4 line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed (placement, order, final "
+                        "availability, RNG state) as DIR/<name>.npy, float64, at most 64 MB")
     p.add_argument("--shard", default="scenarios", choices=["scenarios", "hosts"],
                    help="N > 1: independent scenario per rank (weak scaling, config 4) or one "
                         "round with its host dimension split over the ranks (strong, config 5)")
@@ -90,7 +109,10 @@ def parse():
                    help="1: also time BASELINE configs 1 and 2 -- every schedule() round of the "
                         "recorded reference simulations through the drop-in policy classes; -1 "
                         "(default): with the default workload's extras")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---------------------------------------------------------------------------- launcher
@@ -202,6 +224,40 @@ def check_parity(got, r, ref=None):
     if ref is None:
         ref = oracle.place(r, threads=oracle_threads())
     return same_result(got, ref)
+
+
+# ---------------------------------------------------------------------------- output dump
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 20261015
+
+
+def dump_outputs(path, results):
+    """--dump-outputs: the arrays a caller of the timed path receives -- placement, order, final
+    availability and (opportunistic) the RNG state of every round in ``results``, scenario after
+    scenario -- as ``path``/<name>.npy in float64 (every value is an int32 / uint32 or already a
+    float64, so the conversion is exact). When all of them exceed DUMP_MAX_BYTES, the arrays are
+    taken smallest first and each one larger than its even share of what is left is cut to a
+    fixed, seeded sample of its elements (in index order), the same from run to run. Returns
+    {name: elements written}."""
+    arrays = {}
+    for name in ("placement", "order", "avail", "mt_state"):
+        parts = [getattr(x, name) for x in results]
+        if any(p is None for p in parts):
+            continue
+        arrays[name] = np.concatenate([np.asarray(p, dtype=np.float64).ravel() for p in parts])
+    if sum(a.nbytes for a in arrays.values()) > DUMP_MAX_BYTES:
+        rng = np.random.RandomState(DUMP_SEED)
+        left = DUMP_MAX_BYTES // 8
+        names = sorted(arrays, key=lambda n: (arrays[n].size, n))      # (small arrays whole)
+        for i, name in enumerate(names):
+            a, share = arrays[name], left // (len(names) - i)
+            if a.size > share:
+                arrays[name] = a = a[np.sort(rng.choice(a.size, size=share, replace=False))]
+            left -= a.size
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: int(a.size) for name, a in arrays.items()}
 
 
 # ---------------------------------------------------------------------------- extra workloads
@@ -979,8 +1035,9 @@ def main():
 
     # events around the dominant kernel only (dominant_kernel: found over two untimed steps with
     # every named kernel timed); BENCH_PROF=0: no events at all, for A/B of their cost (the
-    # roofline then has no kernel time), BENCH_PROF=1: every launch
-    prof = int(os.environ.get("BENCH_PROF", "2"))
+    # roofline then has no kernel time), BENCH_PROF=1: every launch. --full only: a plain run
+    # takes no untimed steps beyond the warm-up and records no events
+    prof = int(os.environ.get("BENCH_PROF", "2")) if args.full else 0
     dom, dom_share, dom_kms = dominant_kernel(eng, lambda: (reset(), run(dr))) if prof == 2 else (None, None, {})
     eng.reset_kstats()
     eng.set_profiling(prof, kernel=dom)
@@ -1035,25 +1092,29 @@ def main():
                                 "scenario-sharded x%d (no data-path collective)" % world),
                 "dist_backend": (("gloo" if gloo else "nccl") if world > 1 else None),
             },
-            "roofline": dominant_roofline(mode, H, T, ks, ep, args.steps,
-                                          variant=("_b%d" % B) if B else "",
-                                          rounds_per_step=B or 1, warm=args.warmup),
-            "kernels_ms_per_step": {k: v["ms"] / args.steps for k, v in ks.items() if k in KCLASS_NAMES},
-            "kernel_ms_per_step": {k: v["ms"] / args.steps for k, v in ks["kernels"].items()},
-            "walk_us_per_task": (ks["commit"]["ms"] * 1e3 / args.steps / max(T * (B or 1), 1)
-                                 if not B and ks["commit"]["ms"] > 0 else None),
             "windows_per_step": stats["windows"], "refills_per_step": stats["refills"],
             "epochs_per_step": ep["epochs"], "segments_per_step": ep["segments"],
             "rejected_segments_per_step": ep["rejected"],
             "frontier_chains_per_step": ep.get("frontier_chains"),
             "list_chains_per_step": ep.get("list_chains"),
         }
-        out.update(step_hbm(mode, H, T, ms_per_step, ("_b%d" % B) if B else ""))
+        if args.dump_outputs:
+            out["outputs"] = dump_outputs(args.dump_outputs, dr.results() if B else [dr.result()])
+        if args.full:
+            out["roofline"] = dominant_roofline(mode, H, T, ks, ep, args.steps,
+                                                variant=("_b%d" % B) if B else "",
+                                                rounds_per_step=B or 1, warm=args.warmup)
+            out["kernels_ms_per_step"] = {k: v["ms"] / args.steps for k, v in ks.items()
+                                          if k in KCLASS_NAMES}
+            out["kernel_ms_per_step"] = {k: v["ms"] / args.steps for k, v in ks["kernels"].items()}
+            out["walk_us_per_task"] = (ks["commit"]["ms"] * 1e3 / args.steps / max(T * (B or 1), 1)
+                                       if not B and ks["commit"]["ms"] > 0 else None)
+            out.update(step_hbm(mode, H, T, ms_per_step, ("_b%d" % B) if B else ""))
         ref = None
-        if world == 1 and args.cpu_baseline_seconds > 0:
+        if args.full and world == 1 and args.cpu_baseline_seconds > 0:
             log("[rank 0] cpu baseline (oracle, all cores and 1 thread) ...")
             out["cpu_baseline"], ref = cpu_baseline(r, args.cpu_baseline_seconds)
-        if args.parity:
+        if args.full and args.parity:
             log("[rank 0] parity against the oracle ...")
             if B:
                 from oracle import oracle
@@ -1063,9 +1124,9 @@ def main():
                 out["parity"] = check_parity(dr.result(), r, ref)
         default = (not B and not hosts_sharded and world == 1 and H == DEFAULT_H
                    and T == DEFAULT_T and args.window == 0 and args.pipeline == 1 and args.epochs == 1)
-        if args.extra == 1 or (args.extra < 0 and default):
+        if args.full and (args.extra == 1 or (args.extra < 0 and default)):
             out["extra"] = extra_workloads(eng, args, args.mode)
-        if args.replay == 1 or (args.replay < 0 and default and args.extra != 0):
+        if args.full and (args.replay == 1 or (args.replay < 0 and default and args.extra != 0)):
             out.setdefault("extra", {}).update(replay_workloads(eng))
             try:
                 out["extra"]["c2_lockstep"] = lockstep_workload(eng)
@@ -1073,7 +1134,7 @@ def main():
                 out["extra"]["c2_lockstep"] = {"error": "%s: %s" % (type(e).__name__, e)}
             log("[rank 0] lockstep: %s" % {k: v for k, v in out["extra"]["c2_lockstep"].items()
                                            if k not in ("workload", "cpu_baseline")})
-    if world > 1 and args.c4_batch > 0 and not B:
+    if args.full and world > 1 and args.c4_batch > 0 and not B:
         # (every rank: the barriers and the MAX / MIN reductions are collective)
         c4 = scenario_batch_line(eng, args, rank, world, gloo, args.c4_batch)
         if rank == 0:
@@ -1081,7 +1142,7 @@ def main():
             log("[rank 0] config 4 x%d: %.3e cand/s, %.2f ms, parity %s"
                 % (world, c4["value"], c4["ms_per_step"], c4["parity"]))
     if rank == 0:
-        print(compact_line(out, write_full(out)), flush=True)
+        print(compact_line(out, write_full(out) if args.full else None), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -365,6 +365,12 @@ def main():
             fn = os.path.join(HERE, tr["name"] + ".json.gz")
             with gzip.open(fn, "wt") as f:
                 json.dump(tr, f, separators=(",", ":"))
+            if os.path.getsize(fn) > (1 << 20):      # a committed file stays under 1 MiB: xz
+                import lzma
+                os.remove(fn)
+                fn = fn[:-len(".gz")] + ".xz"
+                with lzma.open(fn, "wt", preset=9 | lzma.PRESET_EXTREME) as f:
+                    json.dump(tr, f, separators=(",", ":"))
             e = tr["e2e"]
             print("%-26s rounds=%d (empty %d) recorded=%d placed=%d makespan=%.3f wall=%.1fs %d KB"
                   % (tr["name"], e["rounds"], e["empty_rounds"], len(tr["rounds"]),

@@ -7,6 +7,7 @@ group structure the reference itself produced) and into the expected outputs.
 import functools
 import gzip
 import json
+import lzma
 import os
 
 import numpy as np
@@ -19,8 +20,15 @@ CASES = ["empty", "one_host", "ties", "exact_fit", "opp_single", "saturate", "pr
          "c1_sim_h100", "c2_h1000", "rt_c1_h100", "rt_h12"]
 
 
+SUFFIXES = (".json.gz", ".json.xz")    # (.xz: a fixture whose .gz would exceed 1 MiB)
+
+
 @functools.lru_cache(maxsize=None)
 def load(name):
+    path = os.path.join(GOLDEN, name + ".json.xz")
+    if os.path.exists(path):
+        with lzma.open(path, "rt") as f:
+            return json.load(f)
     with gzip.open(os.path.join(GOLDEN, name + ".json.gz"), "rt") as f:
         return json.load(f)
 
@@ -133,7 +141,7 @@ def all_runs(skip_errors=True):
 def sim_traces():
     """Names of the recorded reference simulations, e.g. ``sim_c1_cost_aware``."""
     return sorted(f[:-len(".json.gz")] for f in os.listdir(GOLDEN)
-                  if f.startswith("sim_") and f.endswith(".json.gz"))
+                  if f.startswith("sim_") and f.endswith(SUFFIXES))
 
 
 def sim_rounds(name):

@@ -23,7 +23,8 @@ def test_bench_two_ranks_gloo(shard, mode):
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--hosts", "20000", "--tasks", "300", "--mode", mode, "--steps", "2", "--warmup", "1",
-           "--shard", shard, "--cpu-baseline-seconds", "0", "--extra", "0", "--c4-batch", "16"]
+           "--shard", shard, "--full", "--cpu-baseline-seconds", "0", "--extra", "0",
+           "--c4-batch", "16"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -47,7 +48,7 @@ def test_bench_two_ranks_scenario_batch(mode):
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--hosts", "1000", "--tasks", "1000", "--batch", "64", "--mode", mode, "--steps", "2",
-           "--warmup", "1", "--cpu-baseline-seconds", "0", "--extra", "0"]
+           "--warmup", "1", "--full", "--cpu-baseline-seconds", "0", "--extra", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -68,7 +69,7 @@ def test_bench_two_ranks_config4_line_fits():
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
            "--hosts", "20000", "--tasks", "300", "--steps", "2", "--warmup", "1",
-           "--cpu-baseline-seconds", "0", "--extra", "0", "--c4-batch", "512"]
+           "--full", "--cpu-baseline-seconds", "0", "--extra", "0", "--c4-batch", "512"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

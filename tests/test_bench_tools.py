@@ -189,6 +189,36 @@ def test_bench_line_fits_the_driver(world):
         assert c4["n_gpus"] == world and c4["scenarios"] == 512 * world
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files holding exactly the results' values; over the byte
+    limit the small arrays stay whole and the large one is cut to the same seeded sample (in
+    index order) on every call, the total within the limit."""
+    import numpy as np
+    from pivot_place._abi import RoundResult
+    rng = np.random.RandomState(3)
+    res = [RoundResult(placement=rng.randint(-1, 50, 7).astype(np.int32),
+                       order=rng.permutation(7).astype(np.int32),
+                       avail=rng.rand(4, 50), mt_state=None) for _ in range(2)]
+    n = bench.dump_outputs(str(tmp_path / "a"), res)
+    assert n == {"placement": 14, "order": 14, "avail": 400}
+    assert sorted(os.listdir(tmp_path / "a")) == ["avail.npy", "order.npy", "placement.npy"]
+    av = np.load(tmp_path / "a" / "avail.npy")
+    assert av.dtype == np.float64
+    assert np.array_equal(av, np.concatenate([x.avail.ravel() for x in res]))
+    pl = np.load(tmp_path / "a" / "placement.npy")
+    assert pl.dtype == np.float64 and np.array_equal(pl, np.concatenate([x.placement for x in res]))
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 8 * 128)
+    n = bench.dump_outputs(str(tmp_path / "b"), res)
+    assert n == {"placement": 14, "order": 14, "avail": 100}
+    bench.dump_outputs(str(tmp_path / "c"), res)
+    cut = np.load(tmp_path / "b" / "avail.npy")
+    assert np.array_equal(cut, np.load(tmp_path / "c" / "avail.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "order.npy"), np.load(tmp_path / "a" / "order.npy"))
+    it = iter(av)                       # (a subsequence of the whole array, in index order)
+    assert all(any(x == y for y in it) for x in cut)
+    assert 8 * sum(n.values()) <= bench.DUMP_MAX_BYTES
+
+
 def test_bench_line_degrades_instead_of_growing():
     """More extras than the line can hold: the cut gets coarser, the line stays parseable."""
     out = _full_out(1)

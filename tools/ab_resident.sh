@@ -5,7 +5,8 @@ for v in main noskip noscreen noboth; do
   lib=""
   [ "$v" != main ] && lib="pivot-scheduling_amd/diag/libpivot_place_$v.so"
   for m in ${MODES:-ca_bf vbp_ff ca_ff vbp_bf opp}; do
-    PIVOT_PLACE_LIB=$lib timeout -k 10 120 python bench.py --batch 512 --hosts 1000 --tasks 1000 --mode $m --steps 10 --extra 0 --cpu-baseline-seconds 0 --parity 1 > gpurun_out/ab_${v}_$m.log 2>&1 || { echo "fail $v $m"; exit 1; }
-    echo "$v $m $(grep -o "\"ms_per_step\": [0-9.]*\|\"parity\": [a-z]*" gpurun_out/ab_${v}_$m.log | tr "\n" " ")"
+    log=$(mktemp -t ab_${v}_$m.XXXXXX)
+    PIVOT_PLACE_LIB=$lib timeout -k 10 120 python bench.py --batch 512 --hosts 1000 --tasks 1000 --mode $m --steps 10 --full --extra 0 --cpu-baseline-seconds 0 --parity 1 > "$log" 2>&1 || { echo "fail $v $m: $log"; exit 1; }
+    echo "$v $m $(grep -o "\"ms_per_step\": *[0-9.]*\|\"parity\": *[a-z]*" "$log" | tr "\n" " ")"
   done
 done

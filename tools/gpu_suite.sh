@@ -5,7 +5,7 @@
 #   gpurun -- 'tools/gpu_suite.sh tests smoke bench profbench pmc'
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 T="python -u -m pytest -m gpu -x -q --timeout 300 --timeout-method thread"
-NB="--extra 0 --replay 0 --cpu-baseline-seconds 0"
+NB="--full --extra 0 --replay 0 --cpu-baseline-seconds 0"   # (parity and kernel times only)
 run() { tools/gpu_step.sh "$@" || exit $?; }
 for s in "$@"; do
   case $s in
@@ -19,7 +19,7 @@ for s in "$@"; do
     t_opp)      run t_opp 500 $T tests/test_gpu_opp_walk.py tests/test_gpu_parity.py tests/test_gpu_headline.py tests/test_gpu_sharded.py tests/test_gpu_batch.py -k "opp or OPP or opportunistic" ;;
     t_multi)    run t_multi 600 $T tests/test_bench_multirank.py tests/test_gpu_batch.py ;;
     smoke)      run smoke 120 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)      run bench 400 python bench.py ;;
+    bench)      run bench 400 python bench.py --full ;;
     b_cabf)     run b_cabf 150 python bench.py $NB --steps 20 ;;
     b_vbpff)    run b_vbpff 150 python bench.py --mode vbp_ff $NB ;;
     b_caff)     run b_caff 150 python bench.py --mode ca_ff $NB ;;
@@ -32,7 +32,7 @@ for s in "$@"; do
     b_c4)       for w in ${C4W:-4 2}; do for m in ca_bf ca_ff opp vbp_ff vbp_bf; do PVT_RES_WAVES=$w run b_c4_${m}_w$w 120 python bench.py --batch 512 --hosts 1000 --tasks 1000 --mode $m --steps 10 $NB; done; done ;;
     t_res)      run t_res 600 $T tests/test_gpu_batch.py tests/test_gpu_parity.py tests/test_policies.py tests/test_sim_replay.py tests/test_lockstep.py tests/test_gpu_fused.py tests/test_anchor.py ;;
     r_split)    run r_split 300 python tools/replay_split.py sim_c1_cost_aware sim_c2a1000_cost_aware sim_c2a1000_opportunistic sim_c2a1000_vbp_ff ;;
-    b_replay)   run b_replay 300 python bench.py --extra 0 --replay 1 --cpu-baseline-seconds 0 --steps 3 ;;
+    b_replay)   run b_replay 300 python bench.py --full --extra 0 --replay 1 --cpu-baseline-seconds 0 --steps 3 ;;
     b_shard)    run b_shard 200 python bench.py --shard hosts $NB ;;
     st_zw)      for m in ca_bf vbp_ff ca_ff; do run st_$m 120 python tools/zwalk_stamps.py 1000000 10000 libpivot_place_stamps.so $m; done ;;
     st_var)     for v in ${VARS:-stamps}; do for m in ${STM:-ca_bf}; do TAILN=13 run st_${v}_$m 120 python tools/zwalk_stamps.py 1000000 10000 libpivot_place_$v.so $m; done; done ;;
