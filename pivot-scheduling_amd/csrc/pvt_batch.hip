@@ -90,7 +90,7 @@ constexpr int RW_SB = RES_MAX_TASKS / 64; // its suffix minima of the demands, p
 
 struct ResLds {
   int zt, ord, pl, u, cd, ci, mt, slot, lst, wa, wz, ws, wx, wd, total;
-  __host__ __device__ ResLds(int Zb, int Tpad, bool walk = false) {
+  __host__ __device__ ResLds(int Zb, int Tpad, const ResidentSwitches& sw) {
     zt = 0;                                            // csum[Zb*Zb], bsum[Zb*Zb] f64
     ord = (16 * Zb * Zb + 15) & ~15;                   // processing order i32[Tpad]
     pl = ord + 4 * Tpad;                               // placement by position i32[Tpad]
@@ -113,13 +113,15 @@ struct ResLds {
     ws = wz + 4 * RW_MAXH;
     wx = ws + 32 * RW_SB;
     wd = wx + 32 * RW_SB;
-    const int rw_end = walk ? wd + 4 * RW_MAXH : 0;
+    const int rw_end = sw.walks() ? wd + 4 * RW_MAXH : 0;
     total = walk_end > sort_end ? walk_end : sort_end;
     total = rw_end > total ? rw_end : total;
   }
 };
 
-size_t resident_lds_bytes(int Zb, int Tpad, bool walk) { return (size_t)ResLds(Zb, Tpad, walk).total; }
+size_t resident_lds_bytes(int Zb, int Tpad, const ResidentSwitches& sw) {
+  return (size_t)ResLds(Zb, Tpad, sw).total;
+}
 
 __device__ __forceinline__ uint64_t dbits(double x) { return (uint64_t)__double_as_longlong(x); }
 
@@ -871,7 +873,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr bool CA = (MODE == CA_FF || MODE == CA_BF);
   constexpr bool STRICT = (MODE == CA_FF || MODE == VBP_BF);
-  const ResLds Lo(A.Zb, A.Tpad, A.walk != 0);
+  const ResLds Lo(A.Zb, A.Tpad, A.sw);
   const int H = R.n_hosts, T = R.n_tasks, Z = R.n_zones;
   const int tid = threadIdx.x, lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -933,16 +935,15 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   // ca_bf 0.743 vs 0.779 ms at config 4); this path takes over where it stops, on the walked
   // capacities.
   int p_start = 0;
-  if (MODE == CA_BF && (A.walk & 3) && H <= RW_MAXH && T > 0 && !R.rt_bw) {
+  if (MODE == CA_BF && A.sw.walk_ca_bf && H <= RW_MAXH && T > 0 && !R.rt_bw) {
 #ifdef PVT_STAMPS
     const uint64_t tw0 = rstamp();
 #endif
-    // the walking wave: 0, or (A.walk == 2, A/B) one that moves with the workgroup index, so
+    // the walking wave: 0, or (walk_rotate, A/B) one that moves with the workgroup index, so
     // two workgroups sharing a CU need not walk on the same SIMD
-    // (A.walk & 4: no bulk runs in the walk, A/B)
-    const int walker = (A.walk & 3) == 2 ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
+    const int walker = A.sw.walk_rotate ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
     p_start = resident_walk<NT>(R, Lo, smem, ord, pl, csum, bsum, has_groups, walker,
-                                (A.walk & 4) == 0, A.stamps);
+                                A.sw.walk_bulk != 0, A.stamps);
 #ifdef PVT_STAMPS
     if (blockIdx.x == 0 && tid == 0 && A.stamps) {   // walked tasks, walk cycles (block 0)
       A.stamps[8] += (uint64_t)p_start;
@@ -960,12 +961,12 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   }
   // first fit by index (vbp first-fit; cost_aware first-fit without sort_hosts): the whole round
   // walked by one wave (resident_walk_ff), this path then only writes the results
-  if ((MODE == VBP_FF || (MODE == CA_FF && !keyed)) && (A.walk & 8) && H <= RW_MAXH && T > 0) {
+  if ((MODE == VBP_FF || (MODE == CA_FF && !keyed)) && A.sw.walk_ff && H <= RW_MAXH && T > 0) {
 #ifdef PVT_STAMPS
     const uint64_t tw0 = rstamp();
 #endif
-    const int walker = (A.walk & 3) == 2 ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
-    p_start = resident_walk_ff<NT, MODE == CA_FF>(R, Lo, smem, ord, pl, walker, (A.walk & 4) == 0,
+    const int walker = A.sw.walk_rotate ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
+    p_start = resident_walk_ff<NT, MODE == CA_FF>(R, Lo, smem, ord, pl, walker, A.sw.walk_bulk != 0,
                                                   A.stamps);
 #ifdef PVT_STAMPS
     if (blockIdx.x == 0 && tid == 0 && A.stamps) {
@@ -1018,15 +1019,15 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   double* skc = reinterpret_cast<double*>(smem + Lo.slot + 32 * RES_MAXW + 8 * RES_MAXW + 32 * RES_MAXW);
   int sh = -1;
   double sc0 = 0.0, sc1 = 0.0, sc2 = 0.0, sc3 = 0.0;
-  // bulk sticky runs (A.walk & 16: off, A/B); run flags u64[RES_CHUNK / 64] in the staging pad
-  const bool bulk_sticky = (A.walk & 16) == 0;
+  // bulk sticky runs (A/B switch); run flags u64[RES_CHUNK / 64] in the staging pad
+  const bool bulk_sticky = A.sw.bulk_sticky != 0;
   uint64_t* ew = reinterpret_cast<uint64_t*>(c_anc + 2 * RES_CHUNK);
-  // run lists (A.walk & 32: off, A/B; bits 8-15: the minimum remaining run, A/B), for vbp
+  // run lists (A/B switches: off, for every policy, the minimum remaining run), for vbp
   // best-fit only: the other policies' fast winners (one ballot, no score reduction) measured
   // cheaper than a list (config 4 cost_aware first-fit 2.1 vs 0.53 ms with lists for every run)
-  const bool run_lists = (MODE == VBP_BF || (MODE != OPP && (A.walk & 64))) && bulk_sticky &&
-                         (A.walk & 32) == 0;
-  const int list_min = (A.walk >> 8) & 255 ? (A.walk >> 8) & 255 : RES_LIST_MIN;
+  const bool run_lists = (MODE == VBP_BF || (MODE != OPP && A.sw.lists_all)) && bulk_sticky &&
+                         A.sw.run_lists;
+  const int list_min = A.sw.list_min ? A.sw.list_min : RES_LIST_MIN;
   RunEntry* rlw = reinterpret_cast<RunEntry*>(smem + Lo.lst) + wave * RES_LK;   // this wave's list
   // Places the `rem` tasks at positions pos.. (demand d, a run) down run lists; returns rem.
   auto run_list_steps = [&](int pos, int rem, double d0, double d1, double d2, double d3) -> int {
@@ -1650,8 +1651,8 @@ void resident_shape(int maxH, int* waves, int* hpl) {
   *hpl = h;
 }
 
-void launch_resident(int mode, int waves, int hpl, int n, const ResidentArgs& a, hipStream_t st) {
-  const size_t lds = resident_lds_bytes(a.Zb, a.Tpad, a.walk != 0);
+void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const ResidentArgs& a,
+                     hipStream_t st) {
   if (mode == RES_MIXED) {             // (four waves; resident_shape with waves = 4)
     const dim3 grid(n), block(4 * WAVE);
     switch (hpl) {
@@ -1826,7 +1827,7 @@ static hipError_t attrs_mode(int lds) {
 }
 
 hipError_t resident_init_attrs() {
-  const int lds = (int)resident_lds_bytes(ZMAX, RES_MAX_TASKS, true);
+  const int lds = (int)resident_lds_bytes(ZMAX, RES_MAX_TASKS, resident_switches(9, RW_MAXH));   // (with the walk)
   hipError_t e = hipSuccess, r;
   if ((r = attrs_mode<CA_FF>(lds)) != hipSuccess) e = r;
   if ((r = attrs_mode<CA_BF>(lds)) != hipSuccess) e = r;

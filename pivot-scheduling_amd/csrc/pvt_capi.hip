@@ -199,10 +199,7 @@ struct pvt_ctx {
   int t_chain_tab = 1;            // PVT_CHAIN_TAB: 0 = chain tables uploaded before the walk
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
   int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
-  int rwalk = 9;                  // PVT_RWALK: resident one-wave walks, bits 1 cost_aware best-fit, 8
-                                  //   first fit by index, 4 without bulk runs, 2 rotated walker; 0 none;
-                                  //   4-wave path: 16 no bulk sticky runs, 32 no run lists, 64 run lists
-                                  //   for every policy, bits 8-15 the shortest remaining run given a list (A/B)
+  int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
   int fused = 1;                  // PVT_FUSED=0: host batches staged in six launches (A/B)
   int ahead = 0;                  // PVT_AHEAD=1: vbp best-fit walks enqueued ahead (place_ahead;
                                   // measured slower, kept for A/B)
@@ -2190,13 +2187,63 @@ static int ensure_pinned_array(pvt_ctx* ctx, T*& p, size_t& cap, size_t n) {
   return PVT_OK;
 }
 
+// The launch of a batch of resident rounds: its shape from the largest round, the A/B switches,
+// the LDS it needs and the profiling scope's sums.
+struct ResidentPlan {
+  int n = 0, waves = 4, hpl = 1;
+  int Zb = 1, Tpad = 64;          // LDS zone-table stride, sort network size (a power of two)
+  ResidentSwitches sw;
+  size_t lds = 0;
+  double cand = 0.0, bytes = 0.0;
+};
+
+// rounds[idx[k]], k < n (idx NULL: rounds[k]); waves: the preference resident_shape starts from;
+// min_lds: LDS the launch needs beside the placement (the fused batch's grouping phases).
+static ResidentPlan plan_resident(const pvt_ctx* ctx, const pvt_round* rounds, const int* idx, int n,
+                                  int waves, size_t min_lds = 0) {
+  ResidentPlan plan;
+  plan.n = n;
+  int maxH = 1, maxT = 1;
+  for (int k = 0; k < n; k++) {
+    const pvt_round& r = rounds[idx ? idx[k] : k];
+    maxH = std::max(maxH, r.n_hosts);
+    maxT = std::max(maxT, r.n_tasks);
+    plan.Zb = std::max(plan.Zb, r.n_zones);
+    const double c = (double)r.n_tasks * r.n_hosts;
+    plan.cand += c;
+    plan.bytes += c * bytes_per_candidate(r.mode);
+  }
+  plan.waves = waves;
+  resident_shape(maxH, &plan.waves, &plan.hpl);
+  while (plan.Tpad < maxT) plan.Tpad <<= 1;
+  plan.sw = resident_switches(ctx->rwalk, maxH);
+  plan.lds = std::max(resident_lds_bytes(plan.Zb, plan.Tpad, plan.sw), min_lds);
+  return plan;
+}
+
+static ResidentArgs plan_args(const pvt_ctx* ctx, const ResidentPlan& plan, const void* desc, uint32_t* mt) {
+  return ResidentArgs{desc, mt, plan.Zb, plan.Tpad, ctx->stamps, plan.sw};
+}
+
+// mode: the rounds' policy, or RES_MIXED; desc: their descriptors on the device
+static int run_resident(pvt_ctx* ctx, const ResidentPlan& plan, int mode, const void* desc, uint32_t* mt) {
+  {
+    Scope sc(ctx, PVT_K_SCORE, plan.cand, plan.bytes, nullptr, "resident_kernel");
+    launch_resident(mode, plan.waves, plan.hpl, plan.n, plan.lds, plan_args(ctx, plan, desc, mt),
+                    ctx->stream);
+  }
+  HIPCHK(hipGetLastError());
+  ctx->windows = plan.n;
+  ctx->refills = 0;
+  return PVT_OK;
+}
+
 // desc_dev: the rounds' descriptors already on the device (pvt_place_host's staging, MT states
 // at mt_dev): nothing is copied and nothing waited for here; the caller copies back and syncs.
 // mt_dev alone (pvt_place_batch_mt): the rounds' MT19937 states live on the device, [n][625].
 static int place_resident(pvt_ctx* ctx, const pvt_round* rounds, int n,
                           const void* desc_dev = nullptr, uint32_t* mt_dev = nullptr) {
   const int mode = rounds[0].mode;
-  int maxH = 1, maxT = 1, maxZ = 1;
   for (int i = 0; i < n; i++) {
     const pvt_round* r = &rounds[i];
     int rc = check_round(ctx, r);
@@ -2205,34 +2252,11 @@ static int place_resident(pvt_ctx* ctx, const pvt_round* rounds, int n,
     if (!resident_fits(r, PVT_RESIDENT_MAX_HOSTS))
       return fail(ctx, PVT_EUNSUPPORTED, "batch round %d: H=%d T=%d exceeds the resident limits (%d, %d)",
                   i, r->n_hosts, r->n_tasks, PVT_RESIDENT_MAX_HOSTS, PVT_RESIDENT_MAX_TASKS);
-    maxH = std::max(maxH, r->n_hosts);
-    maxT = std::max(maxT, r->n_tasks);
-    maxZ = std::max(maxZ, r->n_zones);
   }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  int waves = ctx->res_waves, hpl = 1;
-  resident_shape(maxH, &waves, &hpl);
-  int tpad = 64;
-  while (tpad < maxT) tpad <<= 1;
-  const int rwalk = ctx->rwalk && maxH <= RW_MAXH ? ctx->rwalk : 0;
-  double cand = 0.0, bytes = 0.0;
-  for (int i = 0; i < n; i++) {
-    const double c = (double)rounds[i].n_tasks * rounds[i].n_hosts;
-    cand += c;
-    bytes += c * bytes_per_candidate(mode);
-  }
-  if (desc_dev) {
-    ResidentArgs ra{desc_dev, mt_dev, maxZ, tpad, ctx->stamps, rwalk};
-    {
-      Scope sc(ctx, PVT_K_SCORE, cand, bytes, nullptr, "resident_kernel");
-      launch_resident(mode, waves, hpl, n, ra, st);
-    }
-    HIPCHK(hipGetLastError());
-    ctx->windows = n;
-    ctx->refills = 0;
-    return PVT_OK;
-  }
+  const ResidentPlan plan = plan_resident(ctx, rounds, nullptr, n, ctx->res_waves);
+  if (desc_dev) return run_resident(ctx, plan, mode, desc_dev, mt_dev);
   int rc;
   // the staged descriptors (and MT states) reach the device by an upload kernel reading their
   // mapped pages when it runs: a new batch waits until the previous batch's upload has run
@@ -2266,20 +2290,13 @@ static int place_resident(pvt_ctx* ctx, const pvt_round* rounds, int n,
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(ctx->ev_rstage, st));
   ctx->rstage_busy = true;
-  ResidentArgs ra{ctx->rdesc.p, mt, maxZ, tpad, ctx->stamps, rwalk};
-  {
-    Scope sc(ctx, PVT_K_SCORE, cand, bytes, nullptr, "resident_kernel");
-    launch_resident(mode, waves, hpl, n, ra, st);
-  }
-  HIPCHK(hipGetLastError());
+  if ((rc = run_resident(ctx, plan, mode, ctx->rdesc.p, mt))) return rc;
   if (host_mt)
     HIPCHK(hipMemcpyAsync(ctx->rmt_host, mt, sizeof(uint32_t) * 625 * n, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   if (host_mt)
     for (int i = 0; i < n; i++)
       std::memcpy(rounds[i].mt_state, ctx->rmt_host + (size_t)i * 625, sizeof(uint32_t) * 625);
-  ctx->windows = n;
-  ctx->refills = 0;
   return PVT_OK;
 }
 
@@ -2501,18 +2518,18 @@ static int check_host_round(pvt_ctx* ctx, const pvt_round* r, pvt_ca_items* it, 
 // The device copy of a host round's zone tables, when they equal the cached ones (s.zt); the
 // cache takes the tables of the first cost_aware round of a call that misses it (one small
 // copy on the stream; every host-array call ends with a synchronisation, so no kernel of an
-// earlier call still reads the old tables).
-static int zone_cache(pvt_ctx* ctx, const pvt_round* r, HostSlot& s) {
+// earlier call still reads the old tables). may_fill = false: a miss leaves s.zt NULL and the
+// round stages its own tables (a batch whose earlier round already reads the cached ones).
+static int zone_cache(pvt_ctx* ctx, const pvt_round* r, HostSlot& s, bool may_fill = true) {
   s.zt = nullptr;
   if (!r->cost || !r->bw || r->n_tasks == 0) return PVT_OK;
   const int Z = r->n_zones;
   const size_t zz = (size_t)Z * Z;
-  auto same = [&]() {
-    return ctx->zt_Z == Z && ctx->zt_host.size() == 2 * zz &&
-           std::memcmp(ctx->zt_host.data(), r->cost, 8 * zz) == 0 &&
-           std::memcmp(ctx->zt_host.data() + zz, r->bw, 8 * zz) == 0;
-  };
-  if (!same()) {
+  const bool hit = ctx->zt_Z == Z && ctx->zt_host.size() == 2 * zz &&
+                   std::memcmp(ctx->zt_host.data(), r->cost, 8 * zz) == 0 &&
+                   std::memcmp(ctx->zt_host.data() + zz, r->bw, 8 * zz) == 0;
+  if (!hit) {
+    if (!may_fill) return PVT_OK;
     ctx->zt_host.resize(2 * zz);
     std::memcpy(ctx->zt_host.data(), r->cost, 8 * zz);
     std::memcpy(ctx->zt_host.data() + zz, r->bw, 8 * zz);
@@ -2726,56 +2743,43 @@ extern "C" int pvt_restore_hosts(pvt_ctx* ctx, double* avail, const double* avai
   return PVT_OK;
 }
 
+// A host batch as staged (pvt_place_host_batch).
+struct HostBatch {
+  pvt_round* rounds;
+  pvt_ca_items* const* items;        // per round, or NULL
+  std::vector<HostSlot> s;           // per round
+  std::vector<int> live, withit;     // the rounds with tasks; those of them with items
+  int mode = -1;                     // the live rounds' policy, or RES_MIXED
+  size_t o_fr = 0, o_ka = 0, o_kg = 0;   // stage offsets: FusedRound[live], AnchorArgs / CaGroupArgs[withit]
+  pvt_ca_items* it(int i) const { return items ? items[i] : nullptr; }
+};
+
 // The staged host batch in ONE launch (resident_fused_kernel, pvt_batch.hip): every round's
 // workgroup copies its ranges of the mapped stage to the device copy, runs its grouping (items)
 // and its placement, and copies its results back; one synchronisation. PVT_FUSED=0: the staged
 // upload / anchor / grouping / placement / download launches instead (A/B).
-static int place_host_fused(pvt_ctx* ctx, pvt_round* rounds, pvt_ca_items* const* items,
-                            int32_t n_rounds, int32_t* rcs, std::vector<HostSlot>& s,
-                            const std::vector<int>& live, const std::vector<int>& withit,
-                            size_t o_fr, size_t o_ka, size_t o_kg, bool mixed, int mode0, int maxH,
-                            int maxT, int maxZ) {
-  hipStream_t st = ctx->stream;
+static int place_host_fused(pvt_ctx* ctx, const HostBatch& B) {
   char* hb = static_cast<char*>(ctx->hst);
-  char* db = static_cast<char*>(ctx->hdev.p);
-  FusedRound* fr = reinterpret_cast<FusedRound*>(hb + o_fr);
-  for (size_t k = 0; k < live.size(); k++) {
-    const HostSlot& h = s[live[k]];
+  FusedRound* fr = reinterpret_cast<FusedRound*>(hb + B.o_fr);
+  for (size_t k = 0; k < B.live.size(); k++) {
+    const HostSlot& h = B.s[B.live[k]];
     fr[k] = FusedRound{(int64_t)h.out_lo, (int64_t)h.out_hi, (int64_t)h.in_lo, (int64_t)h.in_hi,
                        (int64_t)h.desc, -1, 0};
   }
-  for (size_t k = 0; k < withit.size(); k++)
-    for (size_t j = 0; j < live.size(); j++)
-      if (live[j] == withit[k]) fr[j].items = (int32_t)k;
-  int waves = 4, hpl = 1;
-  resident_shape(maxH, &waves, &hpl);
-  int tpad = 64;
-  while (tpad < maxT) tpad <<= 1;
-  double cand = 0.0, bytes = 0.0;
-  for (int i : live) {
-    const double c = (double)rounds[i].n_tasks * rounds[i].n_hosts;
-    cand += c;
-    bytes += c * bytes_per_candidate(rounds[i].mode);
-  }
-  const int rwalk = ctx->rwalk && maxH <= RW_MAXH ? ctx->rwalk : 0;
-  FusedArgs F{static_cast<const char*>(ctx->hst_map), db, (int64_t)o_fr, (int64_t)o_ka,
-              (int64_t)o_kg, ResidentArgs{nullptr, nullptr, maxZ, tpad, ctx->stamps, rwalk}};
-  size_t lds = resident_lds_bytes(maxZ, tpad, rwalk != 0);
-  if (!withit.empty()) lds = std::max(lds, fused_pre_lds_bytes());
+  for (size_t k = 0; k < B.withit.size(); k++)
+    for (size_t j = 0; j < B.live.size(); j++)
+      if (B.live[j] == B.withit[k]) fr[j].items = (int32_t)k;
+  const ResidentPlan plan = plan_resident(ctx, B.rounds, B.live.data(), (int)B.live.size(), 4,
+                                          B.withit.empty() ? 0 : fused_pre_lds_bytes());
+  FusedArgs F{static_cast<const char*>(ctx->hst_map), static_cast<char*>(ctx->hdev.p),
+              (int64_t)B.o_fr, (int64_t)B.o_ka, (int64_t)B.o_kg, plan_args(ctx, plan, nullptr, nullptr)};
   {
-    Scope sc(ctx, PVT_K_SCORE, cand, bytes, nullptr, "resident_fused_kernel");
-    launch_fused(mixed ? RES_MIXED : mode0, hpl, (int)live.size(), lds, F, st);
+    Scope sc(ctx, PVT_K_SCORE, plan.cand, plan.bytes, nullptr, "resident_fused_kernel");
+    launch_fused(B.mode, plan.hpl, plan.n, plan.lds, F, ctx->stream);
   }
   HIPCHK(hipGetLastError());
-  ctx->windows = (int64_t)live.size();
+  ctx->windows = plan.n;
   ctx->refills = 0;
-  HIPCHK(hipStreamSynchronize(st));
-  for (int i : live) {
-    pvt_ca_items* it = items ? items[i] : nullptr;
-    if (it && (rcs[i] = group_error(ctx, hb, s[i], it))) continue;
-    return_round(hb, s[i], &rounds[i], it);
-  }
-  (void)n_rounds;
   return PVT_OK;
 }
 
@@ -2786,15 +2790,15 @@ extern "C" int pvt_place_host_batch(pvt_ctx* ctx, pvt_round* rounds, pvt_ca_item
     return fail(ctx, PVT_EINVAL, "bad host batch (%d rounds)", n_rounds);
   ctx->rs.active = false;
   if (n_rounds == 0) return PVT_OK;
-  std::vector<HostSlot> s(n_rounds);
+  HostBatch B{rounds, items, std::vector<HostSlot>(n_rounds)};
+  std::vector<HostSlot>& s = B.s;
+  std::vector<int>& live = B.live;
+  std::vector<int>& withit = B.withit;
   int rc;
-  // mode0: the first round with tasks (an empty round launches nothing and mixes no modes)
-  int maxH = 1, maxT = 1, maxZ = 1, mode0 = -1;
-  bool mixed = false;
+  bool mixed = false;   // (an empty round launches nothing and mixes no modes)
   for (int i = 0; i < n_rounds; i++) {
-    pvt_ca_items* it = items ? items[i] : nullptr;
     rcs[i] = PVT_OK;
-    if ((rc = check_host_round(ctx, &rounds[i], it, s[i]))) {
+    if ((rc = check_host_round(ctx, &rounds[i], B.it(i), s[i]))) {
       char msg[64];
       std::snprintf(msg, sizeof(msg), "host batch round %d: ", i);
       ctx->err = msg + ctx->err;
@@ -2805,110 +2809,79 @@ extern "C" int pvt_place_host_batch(pvt_ctx* ctx, pvt_round* rounds, pvt_ca_item
                   "(%d, %d): place it with pvt_place_host", i, rounds[i].n_hosts, rounds[i].n_tasks,
                   std::min(ctx->resident_max, (int)PVT_RESIDENT_MAX_HOSTS), PVT_RESIDENT_MAX_TASKS);
     if (rounds[i].n_tasks == 0) continue;
-    maxH = std::max(maxH, rounds[i].n_hosts);
-    maxT = std::max(maxT, rounds[i].n_tasks);
-    maxZ = std::max(maxZ, rounds[i].n_zones);
-    if (mode0 < 0) mode0 = rounds[i].mode;
-    mixed |= rounds[i].mode != mode0;
+    live.push_back(i);
+    if (B.it(i)) withit.push_back(i);
+    mixed |= rounds[i].mode != rounds[live[0]].mode;
   }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
+  if (live.empty()) return PVT_OK;
+  B.mode = mixed ? RES_MIXED : rounds[live[0]].mode;
   // out regions of every round, then the inputs, then the descriptors of the rounds with tasks
   // (contiguous: one resident launch takes them all)
   StageLayout L;
-  for (int i = 0; i < n_rounds; i++)
-    if (rounds[i].n_tasks > 0) plan_out(L, s[i], &rounds[i], items ? items[i] : nullptr);
+  for (int i : live) plan_out(L, s[i], &rounds[i], B.it(i));
   const size_t n_out = L.o;
-  {
-    bool filled = false;               // (the cache takes the first round's tables at most)
-    for (int i = 0; i < n_rounds; i++) {
-      if (rounds[i].n_tasks == 0 || !rounds[i].cost) continue;
-      const int Z = rounds[i].n_zones;
-      const size_t zz = (size_t)Z * Z;
-      const bool hit = ctx->zt_Z == Z && ctx->zt_host.size() == 2 * zz &&
-                       std::memcmp(ctx->zt_host.data(), rounds[i].cost, 8 * zz) == 0 &&
-                       std::memcmp(ctx->zt_host.data() + zz, rounds[i].bw, 8 * zz) == 0;
-      if (hit || !filled) {
-        if ((rc = zone_cache(ctx, &rounds[i], s[i]))) return rc;
-        filled = true;
-      }
-    }
+  // the cached zone tables: refilled at most by the first round that takes them (a later refill
+  // would replace the tables that round reads in the same launch)
+  bool may_fill = true;
+  for (int i : live) {
+    if ((rc = zone_cache(ctx, &rounds[i], s[i], may_fill))) return rc;
+    if (s[i].zt) may_fill = false;
   }
-  for (int i = 0; i < n_rounds; i++)
-    if (rounds[i].n_tasks > 0) plan_in(L, s[i], &rounds[i], items ? items[i] : nullptr);
-  std::vector<int> live, withit;
-  for (int i = 0; i < n_rounds; i++)
-    if (rounds[i].n_tasks > 0) {
-      live.push_back(i);
-      if (items && items[i]) withit.push_back(i);
-    }
-  if (live.empty()) return PVT_OK;
+  for (int i : live) plan_in(L, s[i], &rounds[i], B.it(i));
   // the fused groupings of every cost_aware round: their kernel arguments in the stage, so the
   // anchors and the groups of all of them take three launches
   const int ni = (int)withit.size();
-  const size_t o_ka = ni ? L.take(sizeof(AnchorArgs) * ni) : 0;
+  B.o_ka = ni ? L.take(sizeof(AnchorArgs) * ni) : 0;
   const size_t o_kb = ni ? L.take(sizeof(int32_t) * (ni + 1)) : 0;
-  const size_t o_kg = ni ? L.take(sizeof(CaGroupArgs) * ni) : 0;
+  B.o_kg = ni ? L.take(sizeof(CaGroupArgs) * ni) : 0;
   const size_t o_desc = L.take(sizeof(pvt_round) * live.size());
   for (size_t k = 0; k < live.size(); k++) s[live[k]].desc = o_desc + sizeof(pvt_round) * k;
   const bool fused = ctx->fused != 0;
-  const size_t o_fr = fused ? L.take(sizeof(FusedRound) * live.size()) : 0;
+  B.o_fr = fused ? L.take(sizeof(FusedRound) * live.size()) : 0;
   if ((rc = ensure_pinned(ctx, L.o))) return rc;
   ENSURE(ctx->hdev, L.o);
   char* hb = static_cast<char*>(ctx->hst);
   char* db = static_cast<char*>(ctx->hdev.p);
-  for (int i : live) stage_round(hb, db, s[i], &rounds[i], items ? items[i] : nullptr);
+  for (int i : live) stage_round(hb, db, s[i], &rounds[i], B.it(i));
   int nab = 0;
   for (int k = 0; k < ni; k++) {
     const int i = withit[k];
     AnchorArgs ka;
     CaGroupArgs ga;
     items_args(db, s[i], items[i], &ka, &ga);
-    std::memcpy(hb + o_ka + sizeof(AnchorArgs) * k, &ka, sizeof(AnchorArgs));
-    std::memcpy(hb + o_kg + sizeof(CaGroupArgs) * k, &ga, sizeof(CaGroupArgs));
+    std::memcpy(hb + B.o_ka + sizeof(AnchorArgs) * k, &ka, sizeof(AnchorArgs));
+    std::memcpy(hb + B.o_kg + sizeof(CaGroupArgs) * k, &ga, sizeof(CaGroupArgs));
     reinterpret_cast<int32_t*>(hb + o_kb)[k] = nab;
     nab += anchor_batch_blocks(s[i].C);
   }
   if (ni) reinterpret_cast<int32_t*>(hb + o_kb)[ni] = nab;
-  if (fused) return place_host_fused(ctx, rounds, items, n_rounds, rcs, s, live, withit, o_fr,
-                                     o_ka, o_kg, mixed, mode0, maxH, maxT, maxZ);
-  stage_up(ctx, L.o, st);
-  HIPCHK(hipGetLastError());
-  if (ni) {
-    double np = 0.0;
-    for (int i : withit) np += (double)s[i].NP;
-    Scope sc(ctx, PVT_K_OTHER, 0, 4.0 * np);
-    launch_anchor_batch(reinterpret_cast<const AnchorArgs*>(db + o_ka),
-                        reinterpret_cast<const int32_t*>(db + o_kb), ni, nab, st);
-    launch_ca_groups_batch(reinterpret_cast<const CaGroupArgs*>(db + o_kg), ni, st);
-  }
-  HIPCHK(hipGetLastError());
-  // one resident launch for every round (one workgroup each; mixed policies branch per
-  // workgroup), the MT states read and written through each descriptor's mt_state
-  {
-    int waves = mixed ? 4 : ctx->res_waves, hpl = 1;
-    resident_shape(maxH, &waves, &hpl);
-    int tpad = 64;
-    while (tpad < maxT) tpad <<= 1;
-    double cand = 0.0, bytes = 0.0;
-    for (int i : live) {
-      const double c = (double)rounds[i].n_tasks * rounds[i].n_hosts;
-      cand += c;
-      bytes += c * bytes_per_candidate(rounds[i].mode);
+  if (fused) {
+    if ((rc = place_host_fused(ctx, B))) return rc;
+  } else {
+    stage_up(ctx, L.o, st);
+    HIPCHK(hipGetLastError());
+    if (ni) {
+      double np = 0.0;
+      for (int i : withit) np += (double)s[i].NP;
+      Scope sc(ctx, PVT_K_OTHER, 0, 4.0 * np);
+      launch_anchor_batch(reinterpret_cast<const AnchorArgs*>(db + B.o_ka),
+                          reinterpret_cast<const int32_t*>(db + o_kb), ni, nab, st);
+      launch_ca_groups_batch(reinterpret_cast<const CaGroupArgs*>(db + B.o_kg), ni, st);
     }
-    ResidentArgs ra{db + o_desc, nullptr, maxZ, tpad, ctx->stamps,
-                    ctx->rwalk && maxH <= RW_MAXH ? ctx->rwalk : 0};
-    Scope sc(ctx, PVT_K_SCORE, cand, bytes, nullptr, "resident_kernel");
-    launch_resident(mixed ? RES_MIXED : mode0, waves, hpl, (int)live.size(), ra, st);
+    HIPCHK(hipGetLastError());
+    // one resident launch for every round (one workgroup each; mixed policies branch per
+    // workgroup), the MT states read and written through each descriptor's mt_state
+    const ResidentPlan plan = plan_resident(ctx, rounds, live.data(), (int)live.size(),
+                                            mixed ? 4 : ctx->res_waves);
+    if ((rc = run_resident(ctx, plan, B.mode, db + o_desc, nullptr))) return rc;
+    stage_down(ctx, n_out, st);
+    HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipGetLastError());
-  ctx->windows = (int64_t)live.size();
-  ctx->refills = 0;
-  stage_down(ctx, n_out, st);
-  HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(st));
   for (int i : live) {
-    pvt_ca_items* it = items ? items[i] : nullptr;
+    pvt_ca_items* it = B.it(i);
     if (it && (rcs[i] = group_error(ctx, hb, s[i], it))) continue;
     return_round(hb, s[i], &rounds[i], it);
   }

@@ -496,18 +496,77 @@ constexpr int RES_MAX_HPL = 16;
 constexpr int RES_MAX_HOSTS = RES_THREADS * RES_MAX_HPL;   // 4096
 constexpr int RES_MAX_TASKS = 4096;
 constexpr int RES_MIXED = -1;   // launch_resident: rounds of different policies (4 waves)
+constexpr int RW_MAXH = 1024;   // resident walk: hosts held in LDS
+// The resident kernel's A/B switches, decoded from the PVT_RWALK word (default 9) by
+// resident_switches. One-wave walks (batches whose largest round has at most RW_MAXH hosts):
+//   1  cost_aware best-fit rounds start with the one-wave walk (resident_walk)
+//   8  first fit by index is walked by one wave (resident_walk_ff)
+//   2  the walking wave moves with the workgroup index (2 without 1 also turns the cost_aware
+//      walk on; 3 is 1)
+//   4  no bulk runs in the walks
+// The 4-wave path (every resident size):
+//   16 no bulk sticky runs (and so no run lists)
+//   32 no run lists
+//   64 run lists for every policy but the opportunistic one (default: vbp best-fit only)
+//   bits 8-15 the shortest remaining run given a list (0: RES_LIST_MIN)
+struct ResidentSwitches {     // (one 32-bit kernel argument; all zero: no walk, no bulk runs, no lists)
+  uint32_t walk_ca_bf : 1;    // one-wave walks: cost_aware best-fit,
+  uint32_t walk_ff : 1;       //   first fit by index,
+  uint32_t walk_rotate : 1;   //   the walking wave rotates with the workgroup,
+  uint32_t walk_bulk : 1;     //   bulk runs in the walk
+  uint32_t bulk_sticky : 1;   // 4-wave path: bulk sticky runs,
+  uint32_t run_lists : 1;     //   run lists,
+  uint32_t lists_all : 1;     //   for every policy,
+  uint32_t list_min : 8;      //   from this many remaining tasks (0: RES_LIST_MIN)
+  constexpr bool walks() const { return walk_ca_bf || walk_ff; }   // the walk's LDS region is laid out
+};
+constexpr ResidentSwitches resident_switches(int word, int maxH) {
+  const unsigned w = (unsigned)word;
+  const bool small = maxH <= RW_MAXH;
+  ResidentSwitches s{};
+  s.walk_ca_bf = small && (w & 3) != 0;
+  s.walk_ff = small && (w & 8) != 0;
+  s.walk_rotate = s.walks() && (w & 3) == 2;
+  s.walk_bulk = s.walks() && (w & 4) == 0;
+  s.bulk_sticky = (w & 16) == 0;
+  s.run_lists = (w & 32) == 0;
+  s.lists_all = (w & 64) != 0;
+  s.list_min = w / 256 % 256;   // bits 8-15
+  return s;
+}
+constexpr bool operator==(const ResidentSwitches& a, const ResidentSwitches& b) {
+  return a.walk_ca_bf == b.walk_ca_bf && a.walk_ff == b.walk_ff && a.walk_rotate == b.walk_rotate &&
+         a.walk_bulk == b.walk_bulk && a.bulk_sticky == b.bulk_sticky && a.run_lists == b.run_lists &&
+         a.lists_all == b.lists_all && a.list_min == b.list_min;
+}
+static_assert(sizeof(ResidentSwitches) == 4, "a plain kernel argument of a few bytes");
+static_assert(resident_switches(9, 1024) == ResidentSwitches{1, 1, 0, 1, 1, 1, 0, 0}, "the default");
+static_assert(resident_switches(0, 1024) == ResidentSwitches{0, 0, 0, 0, 1, 1, 0, 0} &&
+              resident_switches(0, 1025) == resident_switches(0, 1024), "0: no walk, the 4-wave defaults");
+static_assert(resident_switches(9, 1025) == resident_switches(0, 1025), "no walk above RW_MAXH hosts");
+static_assert(resident_switches(5, 1024) == ResidentSwitches{1, 0, 0, 0, 1, 1, 0, 0} &&
+              resident_switches(5, 1025) == resident_switches(0, 1025), "5: the cost_aware walk without bulk runs");
+static_assert(resident_switches(16, 1024) == ResidentSwitches{0, 0, 0, 0, 0, 1, 0, 0} &&
+              resident_switches(16, 1025) == resident_switches(16, 1024), "16 holds at every size");
+static_assert(resident_switches(32, 1024) == ResidentSwitches{0, 0, 0, 0, 1, 0, 0, 0} &&
+              resident_switches(32, 1025) == resident_switches(32, 1024), "32 holds at every size");
+static_assert(resident_switches(64 + (12 << 8), 1024) == ResidentSwitches{0, 0, 0, 0, 1, 1, 1, 12} &&
+              resident_switches(64 + (12 << 8), 1025) == resident_switches(64 + (12 << 8), 1024),
+              "64 and the list minimum hold at every size");
+static_assert(resident_switches(2, 1024) == ResidentSwitches{1, 0, 1, 1, 1, 1, 0, 0}, "2: rotated walker");
 struct ResidentArgs {
   const void* rounds;     // device copy of pvt_round[n] (device array pointers)
   uint32_t* mt;           // [n][625] MT19937 states (PVT_OPP; the kernel uses R.mt_state)
   int Zb;                 // zone-table stride in LDS: max n_zones of the batch
   int Tpad;               // power of two >= max n_tasks of the batch (sort network size)
   uint64_t* stamps;       // diagnostic builds only (PVT_STAMPS): block 0 wave 0 phase cycles
-  int walk = 0;           // 1: rounds of <= RW_MAXH hosts start with the one-wave resident walk
+  ResidentSwitches sw;
 };
-constexpr int RW_MAXH = 1024;   // resident walk: hosts held in LDS
-size_t resident_lds_bytes(int Zb, int Tpad, bool walk);
+size_t resident_lds_bytes(int Zb, int Tpad, const ResidentSwitches& sw);
 void resident_shape(int maxH, int* waves, int* hpl);
-void launch_resident(int mode, int waves, int hpl, int n, const ResidentArgs& a, hipStream_t st);
+// lds: resident_lds_bytes of (a.Zb, a.Tpad, a.sw) at least
+void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const ResidentArgs& a,
+                     hipStream_t st);
 hipError_t resident_init_attrs();
 
 // The fused host batch (pvt_place_host_batch): per round (one workgroup of four waves), its byte
@@ -523,7 +582,7 @@ struct FusedArgs {
   char* dev;              // the device copy of the stage
   int64_t o_rounds;       // FusedRound[n] (read from hmap)
   int64_t o_ka, o_kg;     // AnchorArgs[ni], CaGroupArgs[ni] (read from hmap)
-  ResidentArgs ra;        // Zb, Tpad, walk, stamps (rounds unused: each workgroup has its own)
+  ResidentArgs ra;        // Zb, Tpad, sw, stamps (rounds unused: each workgroup has its own)
 };
 size_t fused_pre_lds_bytes();   // LDS of the anchor and grouping phases
 void launch_fused(int mode, int hpl, int n, size_t lds, const FusedArgs& F, hipStream_t st);

@@ -2,6 +2,8 @@
 round trip (one staging copy each way, one resident launch whose workgroups branch on their
 round's mode). Every round must equal the CPU restatement and the same round through
 pvt_place_host alone: placements, order, availability and MT19937 state."""
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -53,6 +55,29 @@ def test_batch_beyond_resident_limits_is_refused(engine):
     assert not engine.host_batch_fits(r)
     with pytest.raises(Exception):
         engine.place_host_batch([(r, None)])
+
+
+def test_rounds_without_zone_tables_after_a_cost_aware_round(engine):
+    """vbp rounds that pass no zone tables (cost and bw NULL; or cost alone) in a batch after a
+    cost_aware round of the same zone count, whose tables the cache then holds: the cache's
+    comparison must leave them alone, and every round equals the CPU restatement."""
+    rounds = _rounds([(_abi.PVT_CA_BF, 1000, 40, 500), (_abi.PVT_VBP_BF, 1000, 47, 501),
+                      (_abi.PVT_VBP_FF, 1000, 54, 502)])
+    assert len({r.n_zones for r in rounds}) == 1
+    n = len(rounds)
+    structs = (_abi.pvt_round * n)()
+    results = []
+    for i, r in enumerate(rounds):
+        structs[i], res = engine._host_struct(r)
+        results.append(res)
+    structs[1].cost = structs[1].bw = None
+    structs[2].bw = None
+    items = (ctypes.POINTER(_abi.pvt_ca_items) * n)()
+    rcs = (ctypes.c_int32 * n)()
+    engine._check(engine.lib.pvt_place_host_batch(engine.ctx, structs, items, n, rcs))
+    for i, (r, g) in enumerate(zip(rounds, results)):
+        assert rcs[i] == _abi.PVT_OK
+        _same(g, oracle.place(r), "round %d mode %d" % (i, r.mode))
 
 
 def test_zone_table_cache_follows_the_tables(engine):

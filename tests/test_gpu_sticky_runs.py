@@ -8,6 +8,7 @@ demands that are not exactly representable (the copy count comes from the sequen
 winners that run out mid-run, lists used up (rebuilt) and lists that run dry (every head a host
 that does not fit: the run's other tasks stay waiting), runs split by the anchor or the group, all-zero rows, and
 realtime bandwidths (runs split by group)."""
+import functools
 import os
 
 import numpy as np
@@ -58,34 +59,67 @@ def _check(engines, rounds, what):
         _same(b, ref, "%s round %d (per-task sticky)" % (what, i))
 
 
+def _edit(r, rs, s):
+    """The demand edit `s` of test_sticky_runs_match_oracle on round r."""
+    if s == 0:                               # two rows only: runs of hundreds of tasks
+        rows = np.array([[0.5, 2048.0], [0.25, 1024.0]])
+        pick = rs.randint(0, 2, size=r.n_tasks)
+        r.dem[0], r.dem[1] = rows[pick, 0], rows[pick, 1]
+    elif s == 1:                             # not exactly representable, tight hosts
+        r.dem[0] = 0.1
+        r.dem[1] = 0.3 * 1024.0
+        r.avail[0] = 0.1 * rs.randint(1, 30, size=r.n_hosts) + 0.05 * (s % 2)
+    elif s == 2:                             # all-zero rows between the others
+        r.dem[:, ::3] = 0.0
+    elif s == 3:                             # one row, few hosts: winners run out mid-run
+        r.dem[0], r.dem[1] = 1.5, 3000.0
+        r.avail[0] = np.minimum(r.avail[0], 4.5)
+    elif s == 4:                             # exact fits (strict modes: the last copy fails)
+        r.dem[0], r.dem[1] = 0.5, 2048.0
+        r.avail[0] = 0.5 * rs.randint(0, 6, size=r.n_hosts)
+        r.avail[1] = 2048.0 * rs.randint(0, 6, size=r.n_hosts)
+    else:                                    # fewer distinct rows: longer runs
+        r.dem[0] = np.round(r.dem[0] * 4) / 4
+        r.dem[1] = np.round(r.dem[1] / 4096.0) * 4096.0
+
+
 @pytest.mark.parametrize("mode,sort_hosts", MODES)
 def test_sticky_runs_match_oracle(engines, mode, sort_hosts):
     rounds = []
     for s in range(6):
         r = synthetic.make_round(mode, 700, 1300, seed=500 + s, sort_hosts=sort_hosts)
-        rs = np.random.RandomState(600 + s)
-        if s == 0:                               # two rows only: runs of hundreds of tasks
-            rows = np.array([[0.5, 2048.0], [0.25, 1024.0]])
-            pick = rs.randint(0, 2, size=r.n_tasks)
-            r.dem[0], r.dem[1] = rows[pick, 0], rows[pick, 1]
-        elif s == 1:                             # not exactly representable, tight hosts
-            r.dem[0] = 0.1
-            r.dem[1] = 0.3 * 1024.0
-            r.avail[0] = 0.1 * rs.randint(1, 30, size=r.n_hosts) + 0.05 * (s % 2)
-        elif s == 2:                             # all-zero rows between the others
-            r.dem[:, ::3] = 0.0
-        elif s == 3:                             # one row, few hosts: winners run out mid-run
-            r.dem[0], r.dem[1] = 1.5, 3000.0
-            r.avail[0] = np.minimum(r.avail[0], 4.5)
-        elif s == 4:                             # exact fits (strict modes: the last copy fails)
-            r.dem[0], r.dem[1] = 0.5, 2048.0
-            r.avail[0] = 0.5 * rs.randint(0, 6, size=r.n_hosts)
-            r.avail[1] = 2048.0 * rs.randint(0, 6, size=r.n_hosts)
-        else:                                    # fewer distinct rows: longer runs
-            r.dem[0] = np.round(r.dem[0] * 4) / 4
-            r.dem[1] = np.round(r.dem[1] / 4096.0) * 4096.0
+        _edit(r, np.random.RandomState(600 + s), s)
         rounds.append(r)
     _check(engines, rounds, "sticky runs mode %d sort_hosts=%s" % (mode, sort_hosts))
+
+
+@functools.lru_cache(maxsize=None)
+def _wide_batch(mode, sort_hosts, H):
+    """Six rounds just past the one-wave walks' limit (RW_MAXH = 1024 hosts: 8 hosts per lane on
+    the 4-wave path) with the edits 0, 3 and 4 above, and their CPU restatements (never changed:
+    shared by the engines)."""
+    rounds = []
+    for s in range(6):
+        r = synthetic.make_round(mode, H, 1300, seed=800 + s, sort_hosts=sort_hosts)
+        _edit(r, np.random.RandomState(900 + s), (0, 3, 4)[s % 3])
+        rounds.append(r)
+    return rounds, [oracle.place(r) for r in rounds]
+
+
+@pytest.fixture(scope="module", params=["9", "16", "32"])
+def wide_engine(request):
+    return request.param, _engine(request.param)
+
+
+@pytest.mark.parametrize("H", [1025, 1100])
+@pytest.mark.parametrize("mode,sort_hosts", MODES)
+def test_switches_hold_above_the_walk_limit(wide_engine, mode, sort_hosts, H):
+    """The 4-wave path's switches (16: no bulk sticky runs, 32: no run lists) take effect in
+    batches of more than RW_MAXH hosts too, and every round still equals the CPU restatement."""
+    rwalk, eng = wide_engine
+    rounds, refs = _wide_batch(mode, sort_hosts, H)
+    for i, (g, ref) in enumerate(zip(eng.place_batch(rounds), refs)):
+        _same(g, ref, "PVT_RWALK=%s mode %d sort_hosts=%s H=%d round %d" % (rwalk, mode, sort_hosts, H, i))
 
 
 @pytest.mark.parametrize("mode", [_abi.PVT_CA_FF, _abi.PVT_CA_BF])
