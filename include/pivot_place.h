@@ -88,25 +88,42 @@ typedef struct pvt_round {
   int32_t sort_tasks;    /* stable sort by descending ||d||2 within each group            */
   int32_t sort_hosts;    /* PVT_CA_FF: order hosts by the frozen key (cost_aware.py:118)  */
   int32_t reserved;      /* must be 0                                                     */
-  double* avail;         /* [4*H] in/out: commits are applied                             */
-  const int32_t* zone;   /* [H] zone index of each host (Host.locality)                   */
-  const uint32_t* tiebreak; /* [H] rank of the host-id string (PVT_VBP_BF), else NULL     */
-  const int32_t* decay;  /* [H] max(len(h.tasks),1) (PVT_CA_FF host_decay), else NULL     */
-  const double* cost;    /* [Z*Z] egress cost, cost[src*Z + dst] (ResourceMetadata.cost);
+  double* avail;         /* [4*H] in/out: commits are applied. Rule 2 (PVT_CHK_AVAIL): every
+                            element finite with a clear sign bit (no -0.0): the engine orders
+                            residuals by their bits                                        */
+  const int32_t* zone;   /* [H] zone index of each host (Host.locality). Rule 1
+                            (PVT_CHK_ZONE): every zone[h] in [0, Z) -- it indexes the zone
+                            tables                                                         */
+  const uint32_t* tiebreak; /* [H] rank of the host-id string (PVT_VBP_BF), else NULL. Rule 10
+                            (PVT_CHK_TIEBREAK, PVT_VBP_BF): ranks < H and distinct (the
+                            violators: an out-of-range rank, and every host but the first
+                            that holds a rank)                                             */
+  const int32_t* decay;  /* [H] max(len(h.tasks),1) (PVT_CA_FF host_decay), else NULL. Rule 9
+                            (PVT_CHK_DECAY, when set): every decay[h] >= 1                 */
+  const double* cost;    /* [Z*Z] egress cost, cost[src*Z + dst] (ResourceMetadata.cost).
+                            Rule 6 (PVT_CHK_COST, cost_aware with T > 0):
                             every cost[a][z] + cost[z][a] >= +0 (egress prices: a score
                             c*r/bw then never grows as a residual r shrinks, and 0 is the
                             least score). Host-array calls (pvt_place_host*) check both
-                            contracts (PVT_EINVAL), device rounds must meet them          */
-  const double* bw;      /* [Z*Z] jittered bandwidth, bw[src*Z + dst]; every bw[a][z] +
+                            contracts (PVT_EINVAL), device rounds must meet them
+                            (pvt_check_round / pvt_set_checks test them on the device)     */
+  const double* bw;      /* [Z*Z] jittered bandwidth, bw[src*Z + dst]. Rule 7 (PVT_CHK_BW,
+                            cost_aware with T > 0): every bw[a][z] +
                             bw[z][a] > 0 (resources/network.py bandwidths are positive: the
                             engine orders cost_aware scores >= +0 by their bits)           */
-  const double* dem;     /* [4*T] task demand (cpus, mem, disk, gpus)                     */
-  const int32_t* task_group;   /* [T] or NULL                                             */
-  const int32_t* group_anchor; /* [G] anchor zone per group, or NULL                      */
+  const double* dem;     /* [4*T] task demand (cpus, mem, disk, gpus). Rule 3 (PVT_CHK_DEM,
+                            T > 0): as rule 2 (suffix maxima of demands prune by bits)     */
+  const int32_t* task_group;   /* [T] or NULL. Rule 4 (PVT_CHK_GROUP, when set and T > 0):
+                            every task_group[t] in [0, G)                                  */
+  const int32_t* group_anchor; /* [G] anchor zone per group, or NULL. Rule 5 (PVT_CHK_ANCHOR,
+                            with task_group and T > 0): every group_anchor[g] in [0, Z)    */
   int32_t* order;        /* [T] out: processing order (task indices)                      */
   int32_t* placement;    /* [T] out: host index, -1 = not placed (task stays waiting)     */
-  uint32_t* mt_state;    /* HOST [625] in/out: MT19937 key[624] then pos (PVT_OPP)        */
-  const double* rt_bw;   /* [G*H] realtime bandwidth per (group, host), or NULL (cost_aware) */
+  uint32_t* mt_state;    /* HOST [625] in/out: MT19937 key[624] then pos (PVT_OPP). Rule 11
+                            (PVT_CHK_MTPOS, PVT_OPP): pos <= 624                           */
+  const double* rt_bw;   /* [G*H] realtime bandwidth per (group, host), or NULL (cost_aware).
+                            Rule 8 (PVT_CHK_RTBW, cost_aware when set): each of the
+                            max(G,1)*H elements finite and > 0                             */
 } pvt_round;
 
 typedef struct pvt_ctx pvt_ctx;
@@ -148,7 +165,7 @@ int  pvt_get_kstats(pvt_ctx* ctx, int kclass, pvt_kstats* out);
  * placement path ("zwalk_kernel", "commit_kernel", "lwalk_kernel", "opp_commit_kernel",
  * "opp_count_kernel", "score_kernel", "band_score_kernel", "perm_scan_kernel", "ordered_kernel",
  * "resident_kernel", "merge_kernel", "merge_small_kernel", "merge_pkg_kernel",
- * "merge_path_kernel"), each bracketed
+ * "merge_path_kernel"; and "check_kernel" of pvt_check_round / pvt_set_checks), each bracketed
  * by its own HIP events on the stream it runs on. An unknown or unlaunched name gives zeros. */
 int  pvt_get_kernel_kstats(pvt_ctx* ctx, const char* kernel, pvt_kstats* out);
 /* With profiling on = 2, record events around the launches of this one named kernel only
@@ -390,6 +407,52 @@ typedef struct pvt_meter_log {
   double* congestion_delay;   /* [S] out                                                  */
 } pvt_meter_log;
 int  pvt_meter(pvt_ctx* ctx, const pvt_meter_log* m);
+
+/*
+ * Opt-in validation of a round's CONTENTS (no reference counterpart). The placement entry points
+ * validate sizes, the mode and NULL pointers only and trust what the arrays hold -- zone, group
+ * and anchor values index tables directly, and the kernels order keys by their bits -- so a caller
+ * that is being brought up can ask first. The rules are numbered as enum pvt_check and stated at
+ * the pvt_round fields they bind. A rule applies only where the engine reads the array.
+ *
+ * pvt_check_round / pvt_check_batch validate the round's structure as pvt_place does (PVT_EINVAL
+ * and friends as there), then run one check kernel over the arrays of all n rounds on the
+ * context's stream, synchronise, and return PVT_OK with one verdict per round in `out`. They read
+ * the rounds' input arrays only and test every index before using it; they never touch order or
+ * placement and never write avail. mt_state (rule 11) is read on the host.
+ *
+ * pvt_set_checks(ctx, 1): pvt_place, pvt_place_batch, pvt_place_batch_mt (its device-resident
+ * MT19937 states are not read: rules 1-10), pvt_shard_begin, pvt_place_host and
+ * pvt_place_host_batch check first. On a violation they launch no placement kernel, write no
+ * output and return PVT_EINVAL. pvt_last_error names the rule, the index and the value (for the
+ * host batch rcs[i] carries each round's own result). Host-array calls check on the host, with
+ * the same predicates, before staging. Off (the default): no entry point issues an extra launch,
+ * copy or synchronisation.
+ */
+enum pvt_check {
+  PVT_CHK_OK = 0,
+  PVT_CHK_ZONE = 1,
+  PVT_CHK_AVAIL = 2,
+  PVT_CHK_DEM = 3,
+  PVT_CHK_GROUP = 4,
+  PVT_CHK_ANCHOR = 5,
+  PVT_CHK_COST = 6,      /* flat index a*Z + z of the zone pair (a, z)                     */
+  PVT_CHK_BW = 7,        /* as PVT_CHK_COST                                                */
+  PVT_CHK_RTBW = 8,
+  PVT_CHK_DECAY = 9,
+  PVT_CHK_TIEBREAK = 10,
+  PVT_CHK_MTPOS = 11     /* index 624                                                      */
+};
+typedef struct pvt_check_report {
+  int32_t code;     /* lowest-numbered violated rule, 0 = none                    */
+  int32_t mask;     /* bit k set: rule k is violated                              */
+  int64_t index;    /* lowest violating flat index of rule `code` (-1 when ok)    */
+  int64_t count;    /* violating elements of rule `code`                          */
+  double  value;    /* the element at `index` (ints converted; rules 6/7: the sum) */
+} pvt_check_report;
+int  pvt_check_round(pvt_ctx* ctx, const pvt_round* r, pvt_check_report* out);
+int  pvt_check_batch(pvt_ctx* ctx, const pvt_round* rounds, int32_t n, pvt_check_report* out);
+int  pvt_set_checks(pvt_ctx* ctx, int on);   /* default 0 */
 
 /* Human-readable text of the last error on this context (static storage of the ctx). */
 const char* pvt_last_error(pvt_ctx* ctx);

@@ -29,6 +29,7 @@
 #include "pvt_anchor.h"
 #include "pvt_groups.h"
 #include "pvt_meter.h"
+#include "pvt_check.h"
 
 using namespace pvt;
 
@@ -238,6 +239,11 @@ struct pvt_ctx {
   std::vector<double> zt_host;
   Buf zt_dev;
   int zt_Z = 0;
+  // content checks (pvt_check_round, pvt_set_checks): off by default
+  int checks = 0;
+  int n_cus = 0;                  // the grid of the check kernel is sized from the CU count
+  std::vector<CheckRound> chk_host;          // the rounds as the check reads them (uploaded)
+  Buf chk_desc, chk_slots, chk_rep, chk_owner;
 };
 
 static int fail(pvt_ctx* c, int code, const char* fmt, ...) {
@@ -404,6 +410,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return PVT_ENODEV;
   pvt_ctx* ctx = new pvt_ctx();
   ctx->device = device;
+  ctx->n_cus = prop.multiProcessorCount;
   std::memset(ctx->ks, 0, sizeof(ctx->ks));
   if (hipSetDevice(device) != hipSuccess ||
       create_streams(ctx, prop.multiProcessorCount) != hipSuccess ||
@@ -457,7 +464,8 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->ksorttmp, &ctx->kflag, &ctx->ep_dev, &ctx->wres, &ctx->hmin, &ctx->cmax, &ctx->fwin,
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
-                 &ctx->zwin, &ctx->brec};
+                 &ctx->zwin, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
+                 &ctx->chk_owner};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->evpool) (void)hipEventDestroy(e);
@@ -865,6 +873,118 @@ static int check_round(pvt_ctx* ctx, const pvt_round* r) {
   if (r->mode == PVT_OPP && !r->mt_state) return fail(ctx, PVT_EINVAL, "opportunistic needs mt_state");
   if (r->mode == PVT_CA_BF && r->decay && r->n_tasks > 0)
     return fail(ctx, PVT_EUNSUPPORTED, "cost_aware best-fit with host_decay (reference crashes, cost_aware.py:26,81)");
+  return PVT_OK;
+}
+
+// ---------------------------------------------------------------- content checks (opt-in)
+static const char* const CHK_NAMES[CHK_RULES + 1] = {
+    "ok", "zone", "avail", "dem", "task_group", "group_anchor", "cost", "bw", "rt_bw", "decay",
+    "tiebreak", "mt_state"};
+
+// i: the round's number in its batch, or -1
+static int fail_check(pvt_ctx* ctx, int i, const pvt_check_report& p) {
+  char where[32] = "";
+  if (i >= 0) std::snprintf(where, sizeof(where), "round %d: ", i);
+  return fail(ctx, PVT_EINVAL, "%scheck failed: rule %d (%s) at index %lld, value %.17g (%lld "
+              "violating, mask 0x%x)", where, p.code, CHK_NAMES[p.code], (long long)p.index, p.value,
+              (long long)p.count, (unsigned)p.mask);
+}
+
+// Rule 11: the MT19937 position, in host memory.
+static void check_mtpos(const pvt_round* r, pvt_check_report* p) {
+  if (r->mode != PVT_OPP || !r->mt_state || !chk_bad_mtpos(r->mt_state[624])) return;
+  p->mask |= 1 << PVT_CHK_MTPOS;
+  if (p->code) return;
+  p->code = PVT_CHK_MTPOS;
+  p->index = 624;
+  p->count = 1;
+  p->value = (double)r->mt_state[624];
+}
+
+// A round of HOST arrays (pvt_place_host*), already through check_round.
+static void check_host_arrays(const pvt_round* r, pvt_check_report* p) {
+  check_on_host(check_describe(*r), p);
+  check_mtpos(r, p);
+}
+
+// n rounds of device arrays: their structure (check_round), then one check launch over all of
+// them on the context's stream, one report per round; synchronises. host_mt: the rounds'
+// mt_state point at host memory (rule 11 is read there).
+static int run_checks(pvt_ctx* ctx, const pvt_round* rounds, int n, pvt_check_report* out,
+                      bool host_mt) {
+  for (int i = 0; i < n; i++) {
+    int rc = check_round(ctx, &rounds[i]);
+    if (rc) return rc;
+  }
+  HIPCHK(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  std::vector<CheckRound>& cr = ctx->chk_host;
+  cr.resize(n);
+  size_t owners = 0;
+  double bytes = 0.0;
+  for (int i = 0; i < n; i++) {
+    cr[i] = check_describe(rounds[i]);
+    if (cr[i].tiebreak) owners += (size_t)cr[i].H;
+    bytes += check_bytes(cr[i]);
+  }
+  const int grid = check_deal(cr.data(), n, ctx->n_cus);
+  ENSURE(ctx->chk_owner, sizeof(uint32_t) * owners);
+  ENSURE(ctx->chk_desc, sizeof(CheckRound) * (size_t)n);
+  ENSURE(ctx->chk_slots, sizeof(CheckSlots) * (size_t)n);
+  ENSURE(ctx->chk_rep, sizeof(pvt_check_report) * (size_t)n);
+  owners = 0;
+  for (int i = 0; i < n; i++)
+    if (cr[i].tiebreak) {
+      cr[i].owner = P<uint32_t>(ctx->chk_owner) + owners;
+      owners += (size_t)cr[i].H;
+    }
+  const CheckRound* desc = P<CheckRound>(ctx->chk_desc);
+  // (cr stays in the context until the synchronisation below: the upload may read it late)
+  HIPCHK(hipMemcpyAsync(ctx->chk_desc.p, cr.data(), sizeof(CheckRound) * (size_t)n, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(ctx->chk_slots.p, 0, sizeof(CheckSlots) * (size_t)n, st));
+  if (owners) {
+    HIPCHK(hipMemsetAsync(ctx->chk_owner.p, 0xff, sizeof(uint32_t) * owners, st));
+    launch_check_owner(desc, n, grid, st);
+  }
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, bytes, nullptr, "check_kernel");
+    launch_check(desc, n, grid, P<CheckSlots>(ctx->chk_slots), st);
+  }
+  launch_check_finish(desc, n, P<CheckSlots>(ctx->chk_slots), P<pvt_check_report>(ctx->chk_rep), st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(out, ctx->chk_rep.p, sizeof(pvt_check_report) * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (host_mt)
+    for (int i = 0; i < n; i++) check_mtpos(&rounds[i], &out[i]);
+  return PVT_OK;
+}
+
+// pvt_set_checks on: the entry point's rounds, before anything of the placement is launched.
+static int gate_checks(pvt_ctx* ctx, const pvt_round* rounds, int n, bool host_mt, bool batch) {
+  std::vector<pvt_check_report> rep((size_t)n);
+  int rc = run_checks(ctx, rounds, n, rep.data(), host_mt);
+  if (rc) return rc;
+  for (int i = 0; i < n; i++)
+    if (rep[i].code) return fail_check(ctx, batch ? i : -1, rep[i]);
+  return PVT_OK;
+}
+
+extern "C" int pvt_check_round(pvt_ctx* ctx, const pvt_round* r, pvt_check_report* out) {
+  if (!ctx || !out) return PVT_EINVAL;
+  if (!r) return fail(ctx, PVT_EINVAL, "null round");
+  return run_checks(ctx, r, 1, out, true);
+}
+
+extern "C" int pvt_check_batch(pvt_ctx* ctx, const pvt_round* rounds, int32_t n, pvt_check_report* out) {
+  if (!ctx) return PVT_EINVAL;
+  if (n < 0 || (n > 0 && (!rounds || !out))) return fail(ctx, PVT_EINVAL, "bad batch (%d rounds)", n);
+  if (n == 0) return PVT_OK;
+  return run_checks(ctx, rounds, n, out, true);
+}
+
+extern "C" int pvt_set_checks(pvt_ctx* ctx, int on) {
+  if (!ctx) return PVT_EINVAL;
+  ctx->checks = on != 0;
   return PVT_OK;
 }
 
@@ -2305,6 +2425,10 @@ extern "C" int pvt_place_batch(pvt_ctx* ctx, const pvt_round* rounds, int32_t n_
   if (n_rounds < 0 || (n_rounds > 0 && !rounds)) return fail(ctx, PVT_EINVAL, "bad batch (%d rounds)", n_rounds);
   ctx->rs.active = false;
   if (n_rounds == 0) return PVT_OK;
+  if (ctx->checks) {
+    int rc = gate_checks(ctx, rounds, n_rounds, true, true);
+    if (rc) return rc;
+  }
   return place_resident(ctx, rounds, n_rounds);
 }
 
@@ -2317,6 +2441,10 @@ extern "C" int pvt_place_batch_mt(pvt_ctx* ctx, const pvt_round* rounds, int32_t
   if (n_rounds == 0) return PVT_OK;
   std::vector<pvt_round> rr(rounds, rounds + n_rounds);   // (mt_state: the device rows, so
   for (int i = 0; i < n_rounds; i++) rr[i].mt_state = mt_dev + (size_t)i * 625;   // checks pass)
+  if (ctx->checks) {                  // (the states are on the device: rules 1-10)
+    int rc = gate_checks(ctx, rr.data(), n_rounds, false, true);
+    if (rc) return rc;
+  }
   return place_resident(ctx, rr.data(), n_rounds, nullptr, mt_dev);
 }
 
@@ -2417,6 +2545,7 @@ extern "C" int pvt_place(pvt_ctx* ctx, const pvt_round* r) {
   if (!ctx) return PVT_EINVAL;
   int rc = check_round(ctx, r);
   if (rc) return rc;
+  if (ctx->checks && (rc = gate_checks(ctx, r, 1, true, false))) return rc;
   if (r->n_tasks > 0 && resident_fits(r, ctx->resident_max)) {
     ctx->rs.active = false;
     return place_resident(ctx, r, 1);
@@ -2457,6 +2586,7 @@ struct HostSlot {
   int C = 0, S = 0, G = 0, GR = 0;
   int64_t NP = 0;
   bool resident = false, dev_mt = false;
+  bool violated = false;              // pvt_set_checks: a content rule failed (check_host_round)
   pvt_round hr{};                     // the round as checked (grouped fields stand in with items)
   pvt_round d{};                      // the device round (arrays in the staging buffer)
 };
@@ -2497,6 +2627,14 @@ static int check_host_round(pvt_ctx* ctx, const pvt_round* r, pvt_ca_items* it, 
   if (it) { s.hr.task_group = &one; s.hr.group_anchor = &one; s.hr.n_groups = 1; }
   int rc = check_round(ctx, &s.hr);
   if (rc) return rc;
+  if (ctx->checks) {   // the content rules, through the predicates the device check uses
+    pvt_check_report p;
+    check_host_arrays(r, &p);
+    if (p.code) {
+      s.violated = true;
+      return fail_check(ctx, -1, p);
+    }
+  }
   if (ca && T > 0)   // host arrays: the zone-table contract of include/pivot_place.h (cost, bw)
     for (int a = 0; a < Z; a++)
       for (int z = 0; z < Z; z++) {
@@ -2796,13 +2934,17 @@ extern "C" int pvt_place_host_batch(pvt_ctx* ctx, pvt_round* rounds, pvt_ca_item
   std::vector<int>& withit = B.withit;
   int rc;
   bool mixed = false;   // (an empty round launches nothing and mixes no modes)
+  std::string violation;   // pvt_set_checks: the first violating round's text
   for (int i = 0; i < n_rounds; i++) {
     rcs[i] = PVT_OK;
     if ((rc = check_host_round(ctx, &rounds[i], B.it(i), s[i]))) {
       char msg[64];
       std::snprintf(msg, sizeof(msg), "host batch round %d: ", i);
       ctx->err = msg + ctx->err;
-      return rc;
+      if (!s[i].violated) return rc;
+      rcs[i] = rc;                   // every round gets its own verdict; nothing is launched
+      if (violation.empty()) violation = ctx->err;
+      continue;
     }
     if (rounds[i].n_tasks > 0 && !s[i].resident)
       return fail(ctx, PVT_EUNSUPPORTED, "host batch round %d: H=%d T=%d exceeds the resident limits "
@@ -2813,6 +2955,7 @@ extern "C" int pvt_place_host_batch(pvt_ctx* ctx, pvt_round* rounds, pvt_ca_item
     if (B.it(i)) withit.push_back(i);
     mixed |= rounds[i].mode != rounds[live[0]].mode;
   }
+  if (!violation.empty()) return fail(ctx, PVT_EINVAL, "%s", violation.c_str());
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   if (live.empty()) return PVT_OK;
@@ -3025,6 +3168,10 @@ extern "C" int pvt_shard_begin(pvt_ctx* ctx, const pvt_round* r, int32_t host_lo
   ctx->rs.pkind = PK_LIST;
   ctx->n_epochs = ctx->n_segs = ctx->n_rejected = 0;
   ctx->n_zchains = ctx->n_gchains = ctx->n_longest = 0;
+  if (ctx->checks) {
+    int rc = gate_checks(ctx, r, 1, true, false);
+    if (rc) return rc;
+  }
   if (r->mode == PVT_OPP) {
     int rc = check_round(ctx, r);
     if (rc) return rc;

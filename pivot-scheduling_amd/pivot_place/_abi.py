@@ -120,6 +120,38 @@ class pvt_kstats(ctypes.Structure):
                 ("candidates", ctypes.c_double), ("bytes", ctypes.c_double)]
 
 
+# Content rules of a round (enum pvt_check; pvt_check_round, pvt_set_checks, pivot_place.checks)
+(PVT_CHK_OK, PVT_CHK_ZONE, PVT_CHK_AVAIL, PVT_CHK_DEM, PVT_CHK_GROUP, PVT_CHK_ANCHOR, PVT_CHK_COST,
+ PVT_CHK_BW, PVT_CHK_RTBW, PVT_CHK_DECAY, PVT_CHK_TIEBREAK, PVT_CHK_MTPOS) = range(12)
+CHECK_NAMES = {PVT_CHK_OK: "ok", PVT_CHK_ZONE: "zone", PVT_CHK_AVAIL: "avail", PVT_CHK_DEM: "dem",
+               PVT_CHK_GROUP: "task_group", PVT_CHK_ANCHOR: "group_anchor", PVT_CHK_COST: "cost",
+               PVT_CHK_BW: "bw", PVT_CHK_RTBW: "rt_bw", PVT_CHK_DECAY: "decay",
+               PVT_CHK_TIEBREAK: "tiebreak", PVT_CHK_MTPOS: "mt_state"}
+
+
+class pvt_check_report(ctypes.Structure):
+    _fields_ = [("code", ctypes.c_int32), ("mask", ctypes.c_int32), ("index", ctypes.c_int64),
+                ("count", ctypes.c_int64), ("value", ctypes.c_double)]
+
+
+@dataclasses.dataclass
+class CheckReport:
+    """Verdict of the content rules on one round (include/pivot_place.h, pvt_check_report)."""
+    code: int = 0          # lowest-numbered violated rule, 0 = none
+    mask: int = 0          # bit k set: rule k is violated
+    index: int = -1        # lowest violating flat index of rule ``code``
+    count: int = 0         # violating elements of rule ``code``
+    value: float = 0.0     # the element at ``index`` (ints converted; rules 6/7: the sum)
+
+    @property
+    def ok(self):
+        return self.code == 0
+
+    @classmethod
+    def from_struct(cls, s):
+        return cls(int(s.code), int(s.mask), int(s.index), int(s.count), float(s.value))
+
+
 @dataclasses.dataclass
 class RoundArrays:
     """One scheduling round in the engine's SoA layout (host numpy arrays).

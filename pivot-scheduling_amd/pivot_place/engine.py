@@ -71,6 +71,10 @@ def load_library(path=None):
         "pvt_set_resident": ([c_void_p, ctypes.c_int32], c_int),
         "pvt_anchor": ([c_void_p, c_void_p], c_int),
         "pvt_meter": ([c_void_p, c_void_p], c_int),
+        "pvt_check_round": ([c_void_p, c_void_p, ctypes.POINTER(_abi.pvt_check_report)], c_int),
+        "pvt_check_batch": ([c_void_p, c_void_p, ctypes.c_int32,
+                             ctypes.POINTER(_abi.pvt_check_report)], c_int),
+        "pvt_set_checks": ([c_void_p, c_int], c_int),
     }
     for name, (args, res) in sig.items():
         f = getattr(lib, name)
@@ -740,6 +744,31 @@ class PlacementEngine:
             return False
         self._check(rc)
         return True
+
+    # -- content checks (include/pivot_place.h, pvt_check_round; pivot_place.checks restates them)
+    def check(self, dr: DeviceRound) -> _abi.CheckReport:
+        """Whether a resident round is one the engine may be given: the content rules of
+        include/pivot_place.h on its arrays, in one check launch. Places nothing."""
+        self._bind_stream()
+        rep = _abi.pvt_check_report()
+        self._check(self.lib.pvt_check_round(self.ctx, ctypes.addressof(dr.struct), ctypes.byref(rep)))
+        return _abi.CheckReport.from_struct(rep)
+
+    def check_batch(self, batch: "DeviceBatch") -> list:
+        """check() of every round of a resident batch in ONE launch; one CheckReport each."""
+        n = len(batch)
+        if n == 0:
+            return []
+        self._bind_stream()
+        reps = (_abi.pvt_check_report * n)()
+        self._check(self.lib.pvt_check_batch(self.ctx, ctypes.addressof(batch.structs), n, reps))
+        return [_abi.CheckReport.from_struct(r) for r in reps]
+
+    def set_checks(self, on=True):
+        """Run the content check in front of every placement call of this engine (default off;
+        a violating round then raises RuntimeError with the rule, index and value, and nothing
+        is placed). For bringing up a new caller."""
+        self._check(self.lib.pvt_set_checks(self.ctx, int(bool(on))))
 
     def set_window(self, tasks):
         self._check(self.lib.pvt_set_window(self.ctx, int(tasks)))
