@@ -312,7 +312,6 @@ __global__ __launch_bounds__(256) void band_score_kernel(BandArgs A) {
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = blockIdx.x * WPB + wave;
   const int t = g / A.S, seg = g % A.S;
-  if (gate_closed(A.gate)) return;
   if (t >= A.nt || (A.nt_dev && t >= *A.nt_dev)) return;
   const double* dp = A.dem + (size_t)t * 4;
   BandList B;

@@ -1,6 +1,6 @@
 // pvt_check_rules.h — the content rules of a round (include/pivot_place.h, pvt_check_round),
 // written once: the device check kernel (pvt_check.hip) and the host-array check of
-// pvt_place_host* (pvt_capi.hip) both call these predicates, so they cannot drift apart. Each
+// pvt_place_host* (pvt_resident.hip) both call these predicates, so they cannot drift apart. Each
 // returns true when the element VIOLATES its rule. pivot_place/checks.py restates them in numpy.
 #pragma once
 #include <stdint.h>

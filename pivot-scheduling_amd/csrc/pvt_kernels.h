@@ -14,7 +14,7 @@
 namespace pvt {
 
 // Timed launches (pvt_set_profiling 2: HIP events around one named kernel). Every launch helper
-// starts its kernel through PVT_LAUNCH. When the profiling scope (pvt_capi.hip Scope) has armed a
+// starts its kernel through PVT_LAUNCH. When the profiling scope (pvt_driver.h Scope) has armed a
 // pair of events, the first launch binds them to the kernel's own dispatch
 // (hipExtLaunchKernelGGL: the events take the dispatch's start and end timestamps), so the timed
 // kernel costs the stream no marker packets. A recorded event pair around a launch left ~5 us of
@@ -127,7 +127,6 @@ struct MergeArgs {
   Lists L;
   const int32_t* nt_dev;  // or NULL: only tasks [0, *nt_dev) (vbp best-fit representative lists)
   int bitonic;            // 1: the bitonic merge_kernel always (A/B; PVT_MERGE_SMALL=0 at ctx create)
-  const int32_t* gate;    // or NULL: enqueued-ahead window (gate_closed below)
 };
 
 // Host-dimension sharding: a rank's exact local lists -> its exchange package (see MergeArgs).
@@ -179,7 +178,7 @@ struct CommitArgs {
   const double* rtb;      // CA_BF realtime_bw: bandwidth per (group, host) [G][H], or NULL
   const int32_t* grp;     // window tasks' groups [nt] (rows of rtb)
   uint64_t* stamps;       // diagnostic builds only (PVT_STAMPS): per-phase cycle sums
-  // Speculative epochs (pvt_capi.hip place_epochs), chain mode when cmap is set: workgroup b
+  // Speculative epochs (pvt_round_epochs.hip place_epochs), chain mode when cmap is set: workgroup b
   // walks the window tasks cmap[coff[b] .. coff[b+1]) (processing order), a chain of group
   // segments whose chain-local starts are cseg[csoff[b] .. csoff[b+1]); it writes wlog[w] for
   // every walked window task w instead of avail, and status[2b] = tasks walked.
@@ -194,12 +193,6 @@ struct CommitArgs {
   // NULL: row w, TaskRec.ord
   const int32_t* rowmap;  //   (row = rowmap[w] - rowbase: the round's run ids, band_runs_kernel)
   const int32_t* ordw;
-  // Windows enqueued ahead (pvt_capi.hip place_ahead; one-wave list walk only): gate = the walk
-  // before's status slot {stopped at, owned hosts, nt, skipped} -- closed (gate_closed) when that
-  // walk was skipped or stopped early: this walk is skipped (status {0, 0, nt, 1}); open: its
-  // owned hosts are this walk's inherited ones (n_prev). ahead: status is such a 4-word slot.
-  const int32_t* gate;
-  int ahead;
   int rowbase;
   // or NULL: mapped pinned words the walk also reports to -- [1] = status[0], [2] = status[1],
   // then [0] = hseq (system-scope release): the host polls them instead of a copy + sync
@@ -334,7 +327,7 @@ void launch_zwalk_keyed(const ZwalkArgs& a, bool strict, hipStream_t st);
 void launch_alive_flags(const double* avail, int H, int lo, int hs, const double* dem, int n,
                         int strict, double* dmin, uint8_t* flags, hipStream_t st);
 
-// Host-sharded frontier walks (pvt_capi.hip pvt_shard_*). A rank's package carries, per chain
+// Host-sharded frontier walks (pvt_shard.hip pvt_shard_*). A rank's package carries, per chain
 // (cost_aware best-fit epochs) or for the one keyed / ordered walk, the first ZW_M window hosts
 // of ITS host range in index order with their capacities, plus its host minima (certificate 2).
 // After the all-gather every rank merges the packages -- ranks own ascending contiguous ranges,
@@ -440,18 +433,8 @@ struct BandArgs {
   int32_t* seg_feas;      // [nt][S]
   const int32_t* nt_dev;  // or NULL: only tasks [0, *nt_dev) (representative lists)
   const uint8_t* ptouched;  // [n] touched by sorted position (= touched[sid[p]], read with the chunk)
-  const int32_t* gate;    // or NULL: enqueued-ahead window (gate_closed)
 };
 
-// An enqueued-ahead window's gate: the status slot {stopped at, owned hosts, nt, skipped} of the
-// walk two windows back for the lists (one back for a walk): closed when that walk was skipped
-// or stopped early -- the window was speculated on a continuation that did not happen.
-__device__ __forceinline__ bool gate_closed(const int32_t* g) {
-  if (!g) return false;
-  const int s = __builtin_amdgcn_readfirstlane(g[3]), a = __builtin_amdgcn_readfirstlane(g[0]);
-  const int n = __builtin_amdgcn_readfirstlane(g[2]);
-  return s != 0 || a != n;
-}
 // A host's snapshot row for the band sort's gather (one 64-byte line per host).
 struct alignas(64) BandRec {
   double a[4];

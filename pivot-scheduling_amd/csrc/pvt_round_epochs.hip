@@ -1,0 +1,392 @@
+// pvt_round_epochs.hip — group-parallel epochs of the windowed round: zero-cost components,
+// the epoch plan and its chain tables, cost_aware best-fit epochs (place_epochs) and the
+// first-fit zero-key epochs of keyed rounds (ff_epoch).
+#include "pvt_driver.h"
+
+// ---------------------------------------------------------------- group-parallel epochs
+// Zones joined by zero egress cost (csum = 0) form one component: a group's winners are the
+// lowest-index fitting hosts of its anchor's component (score 0), so two groups anchored in one
+// component compete for the same hosts and an epoch never holds both (R.ecomp: zone -> root).
+int pvt::zero_cost_components(pvt_ctx* ctx) {
+  RoundState& R = ctx->rs;
+  const pvt_round* r = &R.r;
+  const int Z = R.Z;
+  std::vector<double> cost((size_t)Z * Z);
+  if (R.ginfo && R.cost_host.size() == cost.size()) {
+    cost = R.cost_host;
+  } else {
+    HIPCHK(hipMemcpyAsync(cost.data(), r->cost, sizeof(double) * Z * Z, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  R.ecomp.resize(Z);
+  for (int z = 0; z < Z; z++) R.ecomp[z] = z;
+  auto root = [&](int z) { while (R.ecomp[z] != z) z = R.ecomp[z] = R.ecomp[R.ecomp[z]]; return z; };
+  const int plan = ctx->t_epoch_plan;   // (PVT_EPOCH_PLAN=0: distinct zones only)
+  for (int a = 0; a < Z && plan; a++)
+    for (int z = 0; z < Z; z++)
+      if (cost[(size_t)a * Z + z] + cost[(size_t)z * Z + a] == 0.0) R.ecomp[root(a)] = root(z);
+  for (int z = 0; z < Z; z++) R.ecomp[z] = root(z);
+  return PVT_OK;
+}
+
+// cost_aware best-fit rounds of several groups (pvt_epoch.hip). The groups in processing
+// order, from the caller's task_group / group_anchor (a group's tasks are contiguous).
+int pvt::epoch_groups(pvt_ctx* ctx) {
+  RoundState& R = ctx->rs;
+  const pvt_round* r = &R.r;
+  R.egs.clear();
+  R.ega.clear();
+  const int T = R.T;
+  if (!ctx->epochs || r->mode != PVT_CA_BF || !r->task_group || r->n_groups < 2 || T < 2) return PVT_OK;
+  hipStream_t st = ctx->stream;
+  int rc;
+  std::vector<int> cnt(r->n_groups, 0);
+  std::vector<int32_t> ga;
+  if (R.ginfo) {                              // copied by build_order
+    for (int g = 0; g < r->n_groups; g++) cnt[g] = R.gcnt[g];
+    ga = R.ga_host;
+  } else {
+    std::vector<int32_t> tg(T);
+    ga.resize(r->n_groups);
+    HIPCHK(hipMemcpyAsync(tg.data(), r->task_group, sizeof(int32_t) * T, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(ga.data(), r->group_anchor, sizeof(int32_t) * r->n_groups,
+                          hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (int t = 0; t < T; t++) {
+      if (tg[t] < 0 || tg[t] >= r->n_groups) return fail(ctx, PVT_EINVAL, "task_group out of range");
+      cnt[tg[t]]++;
+    }
+  }
+  int off = 0, ng = 0;
+  for (int g = 0; g < r->n_groups; g++) {
+    if (cnt[g] == 0) continue;
+    R.egs.push_back(off);
+    R.ega.push_back(ga[g]);
+    off += cnt[g];
+    ng++;
+  }
+  R.egs.push_back(T);
+  if ((rc = zero_cost_components(ctx))) return rc;
+  // worth it when groups are many and short (a group longer than a walk's window is walked in
+  // sequential epochs of one segment, without the score / walk pipeline of place_pipelined)
+  if (ng < 2 || T > ng * MAX_WINDOW) { R.egs.clear(); R.ega.clear(); }
+  return PVT_OK;
+}
+
+void pvt::epoch_plan(const RoundState& R, int t0, EpochPlan& P, bool whole) {
+  P.off.assign(1, 0);
+  P.chain.clear(); P.cstart.clear(); P.segs.clear(); P.len.clear();
+  size_t g = 0;
+  while (g + 1 < R.egs.size() && R.egs[g + 1] <= t0) g++;
+  std::vector<int> chain_of(R.ecomp.size() + 1, -1);
+  int t = t0;
+  while (t < R.T && (int)P.chain.size() < EPOCH_SEGS) {
+    const int ge = R.egs[g + 1];
+    const int z = R.ega[g];
+    const int comp = (z >= 0 && z < (int)R.ecomp.size()) ? R.ecomp[z] : (int)R.ecomp.size();
+    int c = chain_of[comp];
+    if (c < 0) {
+      c = chain_of[comp] = (int)P.segs.size();
+      P.segs.emplace_back();
+      P.len.push_back(0);
+    }
+    const int take = std::min({ge - t, CHAIN_MAX - P.len[c], t0 + EPOCH_MAX - t});
+    if (take <= 0 || (whole && take < ge - t)) {
+      if (P.len[c] == 0) { P.segs.pop_back(); P.len.pop_back(); }   // (a chain opened for it)
+      break;
+    }
+    P.segs[c].push_back((int)P.chain.size());
+    P.chain.push_back(c);
+    P.cstart.push_back(P.len[c]);
+    P.len[c] += take;
+    t += take;
+    P.off.push_back(t - t0);
+    if (t < ge) break;
+    g++;
+  }
+}
+
+// The epoch's chain tables to the device (one upload): segment offsets / chains / chain-local
+// starts, per chain its task range in cmap and its segments' chain-local starts.
+int pvt::upload_chain_tables(pvt_ctx* ctx, const EpochPlan& E) {
+  int32_t* host = ctx->ep_host;
+  const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
+  for (int k = 0; k <= nseg; k++) host[EP_SEG_OFF + k] = E.off[k];
+  for (int k = 0; k < nseg; k++) { host[EP_SEG_CHAIN + k] = E.chain[k]; host[EP_SEG_CSTART + k] = E.cstart[k]; }
+  int nm = 0, ns = 0;
+  for (int c = 0; c < nch; c++) {
+    host[EP_COFF + c] = nm;
+    host[EP_CSOFF + c] = ns;
+    for (int sg : E.segs[c]) {
+      host[EP_CSEG + ns++] = E.cstart[sg];
+      for (int w = E.off[sg]; w < E.off[sg + 1]; w++) host[EP_CMAP + nm++] = w;
+    }
+  }
+  host[EP_COFF + nch] = nm;
+  host[EP_CSOFF + nch] = ns;
+  launch_upload(ctx->ep_hdev, ctx->ep_dev.p, sizeof(int32_t) * (EP_CMAP + nm), ctx->stream);
+  HIPCHK(hipGetLastError());
+  return PVT_OK;
+}
+
+// The same tables by value for the frontier walk (ChainTab: no upload launch); false when the
+// epoch does not fit them (the caller uploads instead).
+static_assert(EPOCH_SEGS == CT_SEGS, "chain tables by value hold every epoch segment");
+static bool chain_tab(pvt_ctx* ctx, const EpochPlan& E, ChainTab& t) {
+  const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
+  if (nseg < 1 || nseg > CT_SEGS || nch < 1 || nch > CT_SEGS) return false;
+  for (int c = 0; c < nch; c++)
+    if (E.len[c] > CHAIN_MAX) return false;
+  int32_t* dev = P<int32_t>(ctx->ep_dev);
+  t.nseg = nseg;
+  t.nch = nch;
+  for (int k = 0; k <= nseg; k++) t.seg_off[k] = E.off[k];
+  for (int k = 0; k < nseg; k++) { t.seg_chain[k] = E.chain[k]; t.seg_cstart[k] = E.cstart[k]; }
+  int nm = 0, ns = 0;
+  for (int c = 0; c < nch; c++) {
+    t.coff[c] = nm;
+    t.csoff[c] = ns;
+    for (int sg : E.segs[c]) t.csegid[ns++] = sg;
+    nm += E.len[c];
+  }
+  t.coff[nch] = nm;
+  t.csoff[nch] = ns;
+  t.o_seg_off = dev + EP_SEG_OFF;
+  t.o_seg_chain = dev + EP_SEG_CHAIN;
+  t.o_seg_cstart = dev + EP_SEG_CSTART;
+  t.o_coff = dev + EP_COFF;
+  return true;
+}
+
+// cost_aware first-fit with sort_hosts (cost_aware.py:99-127): an epoch of WHOLE groups from
+// the group start R.t0, chains of zero-cost components walked side by side by the first-fit
+// zero-key chain walk (pvt_zwalk.hip, FF). Every task it proves takes the lowest-index strictly
+// fitting host of its anchor's zero-cost zones -- the first host of the frozen key order -- and
+// chains of different components touch disjoint hosts that are never zero-key for another
+// chain's anchors, so no pair validation is needed. Groups are accepted whole, in order, up to
+// the first one a chain did not complete (the keyed path then takes that group from its start,
+// computing its frozen key on the capacities at the group start, as the reference does).
+int pvt::ff_epoch(pvt_ctx* ctx, int* adv_out) {
+  RoundState& R = ctx->rs;
+  const pvt_round* r = &R.r;
+  hipStream_t st = ctx->stream;
+  *adv_out = 0;
+  const int t0 = R.t0;
+  EpochPlan E;
+  epoch_plan(R, t0, E, true);
+  const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
+  if (nseg == 0 || nch == 0) return PVT_OK;
+  const int nt = E.off.back();
+  ENSURE(ctx->ep_dev, sizeof(int32_t) * EP_WORDS);
+  ENSURE(ctx->wres, sizeof(WinRec) * (size_t)EPOCH_MAX);
+  ENSURE(ctx->hmin, sizeof(double) * 4 * ZW_MIN_PARTS);
+  int32_t* dev = P<int32_t>(ctx->ep_dev);
+  int32_t* host = ctx->ep_host;
+  int rc;
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, 0);
+    launch_host_absmax(r->avail, R.H, 0, R.H, P<double>(ctx->hmin), st);
+  }
+  ZwalkArgs za = zwalk_chain_args(ctx, t0);
+  if (!(ctx->t_chain_tab && chain_tab(ctx, E, za.tab)) && (rc = upload_chain_tables(ctx, E))) return rc;
+  {
+    Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
+    launch_zwalk_ff(za, nch, st);
+  }
+  EpochArgs ea = epoch_args(ctx, t0, nt, nseg);
+  ea.whole = 1;
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, 0);
+    launch_epoch_final(ea, st);
+    launch_epoch_accept_apply(ea, dev + EP_RES, nch, st, ctx->ep_hdev + EP_STATUS,
+                              EP_WORDS - EP_STATUS);   // (readback: mapped)
+  }
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
+  ctx->n_epochs++;
+  ctx->n_segs += nseg;
+  int proven = 0;
+  for (int c = 0; c < nch; c++) proven += host[EP_STATUS + 2 * c] == E.len[c];
+  ctx->n_zchains += proven;
+  ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
+  ctx->n_rejected += host[EP_RES + 3];
+  const int adv = host[EP_RES + 1];
+  if (adv < 0 || adv > nt) return fail(ctx, PVT_EHIP, "first-fit epoch returned %d of %d tasks", adv, nt);
+  *adv_out = adv;
+  return PVT_OK;
+}
+
+// A frontier-walked epoch's verdict (validation, accepted prefix and its apply ran on the
+// device; ctx->ep_host holds the readback): chains left unproven, and the tasks accepted.
+int pvt::epoch_frontier_verdict(pvt_ctx* ctx, const EpochPlan& E, int t0, int* need_out, int* adv_out) {
+  const int32_t* host = ctx->ep_host;
+  const int nch = (int)E.segs.size();
+  int need = 0;
+  for (int c = 0; c < nch; c++) need += host[EP_STATUS + 2 * c] != E.len[c];
+  ctx->n_zchains += nch - need;
+  ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
+  if (host[EP_RES + 4])
+    return fail(ctx, PVT_EHIP, "commit walk: ring hand-off timed out (epoch at task %d)", t0);
+  const int adv = host[EP_RES + 1];
+  // (a segment cut short here is a frontier-walk fallback, not a list refill: the chains the
+  // walk could not prove are walked with lists next; the tasks it proved are accepted)
+  ctx->n_rejected += host[EP_RES + 3];
+  if (adv <= 0 && !need) return fail(ctx, PVT_EHIP, "epoch made no progress at task %d", t0);
+  *need_out = need;
+  *adv_out = adv;
+  return PVT_OK;
+}
+
+int pvt::place_epochs(pvt_ctx* ctx) {
+  RoundState& R = ctx->rs;
+  const pvt_round* r = &R.r;
+  hipStream_t st = ctx->stream;
+  ENSURE(ctx->ep_dev, sizeof(int32_t) * EP_WORDS);
+  ENSURE(ctx->wres, sizeof(WinRec) * (size_t)EPOCH_MAX);
+  ENSURE(ctx->owned[0], sizeof(int32_t) * (size_t)CHAIN_MAX);
+  ENSURE(ctx->l_e[0], sizeof(ListEntry) * (size_t)EPOCH_MAX * LMAX);
+  ENSURE(ctx->l_ids[0], sizeof(int32_t) * (size_t)EPOCH_MAX * LMAX);
+  ENSURE(ctx->l_t[0], sizeof(TaskRec) * (size_t)EPOCH_MAX);
+  int32_t* dev = P<int32_t>(ctx->ep_dev);
+  int32_t* host = ctx->ep_host;
+  EpochPlan E;
+  int t0 = 0, rc;
+  bool force_lists = false;       // the last epoch's frontier walk left chains unproven
+  bool big = false;               // ... because a chain outgrew its window: retry with ZW_MBIG
+  int big_t0 = -1;                //   (at most once per epoch start)
+  R.in_epoch = true;
+  struct Reset { bool& f; ~Reset() { f = false; } } reset_{R.in_epoch};
+  const bool zw_possible = ctx->zwalk && !r->rt_bw && R.Z <= ZMAX;
+  while (t0 < R.T) {
+    // the frontier walk's host minima (certificate 2) depend only on the epoch's start state:
+    // reduced while the host plans the epoch
+    if (zw_possible && !force_lists && !(R.hmin_pre && t0 == 0)) {
+      ENSURE(ctx->hmin, sizeof(double) * 4 * ZW_MIN_PARTS);
+      Scope sc(ctx, PVT_K_OTHER, 0, 0);
+      launch_host_min(r->avail, R.H, 0, R.H, P<double>(ctx->hmin), st);
+    }
+    R.hmin_pre = false;
+    epoch_plan(R, t0, E);
+    const int nseg = (int)E.chain.size(), nch = (int)E.segs.size(), nt = E.off.back();
+    ctx->n_epochs++;
+    ctx->n_segs += nseg;
+    // chains the zero-cost frontier walk can prove need no candidate lists (pvt_zwalk.hip);
+    // the lists are scored only for the others
+    const bool zw = ctx->zwalk && nch > 1 && !r->rt_bw && R.Z <= ZMAX && !force_lists;
+    force_lists = false;
+    if (!zw && (rc = window_lists(ctx, t0, nt, 0, st))) return rc;
+    if (nch == 1) {                           // one chain: the plain walk (writes avail)
+      if ((rc = walk_launch(ctx, t0, nt, 0, 0))) return rc;
+      int adv = 0;
+      if ((rc = walk_status(ctx, t0, nt, false, &adv))) return rc;
+      if (adv < nt) ctx->refills++;
+      t0 += adv;
+      continue;
+    }
+    // (the frontier walk takes the chain tables by value: no upload)
+    ChainTab tab{};
+    const bool tabv = zw && ctx->t_chain_tab && chain_tab(ctx, E, tab);
+    if (!tabv && (rc = upload_chain_tables(ctx, E))) return rc;
+    // (the rejection flags are zeroed by epoch_final_kernel, launched before every validation)
+    int need = nch;                           // chains left to the list walk
+    EpochArgs ea = epoch_args(ctx, t0, nt, nseg);
+    ea.rtb = r->rt_bw;
+    auto validate_and_read = [&]() -> int {
+      {
+        Scope sc(ctx, PVT_K_OTHER, 0, 0);
+        launch_epoch_validate(ea, st);
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(host + EP_STATUS, dev + EP_STATUS, sizeof(int32_t) * (EP_WORDS - EP_STATUS),
+                            hipMemcpyDeviceToHost, st));
+      HIPCHK(hipStreamSynchronize(st));
+      return PVT_OK;
+    };
+    if (zw) {
+      ENSURE(ctx->cmax, sizeof(double) * 4 * EPOCH_SEGS);
+      ZwalkArgs za = zwalk_chain_args(ctx, t0);
+      za.cmax = P<double>(ctx->cmax);
+      // (the first epoch starts from the snapshot the grouped order's launch built its windows from)
+      if (R.zpre && t0 == 0 && !big) za.zpre = P<ZoneWindows>(ctx->zwin);
+      if (tabv) za.tab = tab;
+      R.zpre = false;
+      ea.cmax = P<double>(ctx->cmax);
+      ea.coff = dev + EP_COFF;
+      ea.nch = nch;
+      ea.safe = dev + EP_SAFE;
+      {
+        Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
+        if (big) launch_zwalk_big(za, nch, st);
+        else launch_zwalk(za, nch, st);
+      }
+      const bool was_big = big;
+      big = false;
+      HIPCHK(hipGetLastError());
+      // validation, the accepted prefix and its apply all on the device, then one readback. A
+      // chain the frontier walk could not prove is not accepted past its first segment; the
+      // next epoch then walks its chains with candidate lists (force_lists) -- or, when a chain
+      // only ran out of window hosts, once more with the large window.
+      {
+        Scope sc(ctx, PVT_K_OTHER, 0, 0);
+        launch_epoch_validate(ea, st);
+        launch_epoch_accept_apply(ea, dev + EP_RES, nch, st, ctx->ep_hdev + EP_STATUS,
+                                  EP_WORDS - EP_STATUS);   // (readback: mapped)
+      }
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipStreamSynchronize(st));
+      int adv = 0;
+      if ((rc = epoch_frontier_verdict(ctx, E, t0, &need, &adv))) return rc;
+      if (need && adv < nt) {
+        bool exhausted = false;
+        for (int c = 0; c < nch; c++) exhausted |= host[EP_STATUS + 2 * c + 1] == 2;
+        if (exhausted && !was_big && big_t0 != t0 + adv) {
+          big = true;
+          big_t0 = t0 + adv;
+        } else {
+          force_lists = true;
+        }
+      }
+      t0 += adv;
+      continue;
+    }
+    ctx->n_gchains += need;
+    ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
+    CommitArgs ca_ = commit_args(ctx, t0, nt, 0, 0, dev + EP_STATUS);
+    ca_.prev_ids = nullptr;
+    ca_.coff = dev + EP_COFF;
+    ca_.cmap = dev + EP_CMAP;
+    ca_.csoff = dev + EP_CSOFF;
+    ca_.cseg = dev + EP_CSEG;
+    ca_.wlog = P<WinRec>(ctx->wres);
+    ca_.skip_done = zw ? 1 : 0;
+    if (need) {
+      {
+        Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "commit_kernel");
+        launch_commit_chains(ca_, nch, st);
+      }
+      if ((rc = validate_and_read())) return rc;
+    }
+    // the exact prefix: segments before the first rejected one, up to and including the first
+    // that its chain did not finish (its walked tasks are exact; the next epoch starts there)
+    for (int c = 0; c < nch; c++)
+      if (host[EP_STATUS + 2 * c] == -1)
+        return fail(ctx, PVT_EHIP, "commit walk: ring hand-off timed out (epoch at task %d)", t0);
+    int acc = 0, next = t0;
+    for (int j = 0; j < nseg; j++) {
+      const int len = E.off[j + 1] - E.off[j];
+      const int adv = std::max(0, std::min(len, host[EP_STATUS + 2 * E.chain[j]] - E.cstart[j]));
+      if (j > 0 && host[EP_BAD + j]) { ctx->n_rejected += nseg - j; break; }
+      acc = j + 1;
+      next = t0 + E.off[j] + adv;
+      if (adv < len) { ctx->refills++; ctx->n_rejected += nseg - j - 1; break; }
+    }
+    if (next == t0) return fail(ctx, PVT_EHIP, "epoch made no progress at task %d", t0);
+    {
+      Scope sc(ctx, PVT_K_OTHER, 0, 0);
+      launch_epoch_apply(ea, acc, nch, st);
+    }
+    HIPCHK(hipGetLastError());
+    t0 = next;
+  }
+  return PVT_OK;
+}

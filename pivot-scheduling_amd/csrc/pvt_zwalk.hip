@@ -40,7 +40,7 @@
 // a positive key is >= 2^-899, never 0); (3') as (3), and the chain's demands are >= 0 (a host
 // that strictly fits then has r > 0). Chains of different zero-cost components commit to
 // disjoint hosts, none of which is zero-key for another component's anchors, so every chain's
-// proven prefix is exact in the sequential order too (pvt_capi.hip ff_epoch: no validation).
+// proven prefix is exact in the sequential order too (the driver's ff_epoch: no validation).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -223,12 +223,12 @@ __device__ __forceinline__ uint64_t zstamp() {
 }
 #endif
 
-// KEYED: cost_aware first-fit with sort_hosts (pvt_capi.hip keyed_frontier): one group, its
+// KEYED: cost_aware first-fit with sort_hosts (the driver's round_next_window): one group, its
 // window the first ZW_M hosts of the group's zero-key prefix (perm, index order), strict fit,
 // no zone certificates (the order is the keyed path's own); the window's capacities are written
 // back at the end and status[0] = tasks walked.
 // KEYED with STRICT = false: vbp first-fit (index order, fit >=) over a window of the first
-// alive hosts (pvt_capi.hip ordered_frontier), same mechanics.
+// alive hosts (the driver's ordered_frontier), same mechanics.
 template <bool KEYED, bool STRICT, bool FF = false, int WM = ZW_M>
 __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   static_assert(!FF || (!KEYED && STRICT), "FF: chain mode, strict fit");

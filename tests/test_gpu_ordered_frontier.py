@@ -1,4 +1,4 @@
-"""GPU parity of the ordered frontier walk (pvt_capi.hip ordered_frontier over pvt_zwalk.hip's
+"""GPU parity of the ordered frontier walk (pvt_round.hip ordered_frontier over pvt_zwalk.hip's
 keyed mode): vbp first-fit (fit >=, reference scheduler/vbp.py) and cost_aware first-fit without
 sort_hosts (strict fit, reference scheduler/cost_aware.py) take the first host in index order
 that fits; the walk does that over a window of the first 1024 hosts that fit the smallest
