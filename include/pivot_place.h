@@ -37,6 +37,13 @@ extern "C" {
 
 #define PVT_ABI_VERSION 3
 
+/* Zones of a round: 1 <= pvt_round.n_zones <= PVT_MAX_ZONES at every entry point that takes a
+ * round; more is PVT_EINVAL and nothing is written. Up to 32 zones a round runs the fast paths
+ * (zone tables in LDS, zero-cost frontier walks, group epochs, one-wave resident walks); from 33
+ * on the same policies run bit-exactly on the list-based windows and the wide resident kernels,
+ * which read the Z x Z tables from global memory. pvt_max_zones() is the loaded library's bound. */
+#define PVT_MAX_ZONES 512
+
 /* Return codes. */
 #define PVT_OK            0
 #define PVT_EINVAL       -1   /* bad argument (null pointer, size, mode)          */
@@ -83,7 +90,7 @@ typedef struct pvt_round {
   int32_t mode;          /* enum pvt_mode                                                 */
   int32_t n_hosts;       /* H >= 1                                                        */
   int32_t n_tasks;       /* T >= 0                                                        */
-  int32_t n_zones;       /* Z >= 1 (cost/bw are Z x Z)                                    */
+  int32_t n_zones;       /* 1 <= Z <= PVT_MAX_ZONES (cost/bw are Z x Z)                   */
   int32_t n_groups;      /* G (cost_aware); ignored when task_group is NULL               */
   int32_t sort_tasks;    /* stable sort by descending ||d||2 within each group            */
   int32_t sort_hosts;    /* PVT_CA_FF: order hosts by the frozen key (cost_aware.py:118)  */
@@ -146,6 +153,7 @@ enum pvt_kclass {
 };
 
 int  pvt_abi_version(void);
+int  pvt_max_zones(void);   /* PVT_MAX_ZONES of the loaded library */
 int  pvt_ctx_create(int device, pvt_ctx** out);
 int  pvt_ctx_destroy(pvt_ctx* ctx);
 /* Order the context's work on a caller stream (hipStream_t as void*), e.g.
@@ -258,12 +266,17 @@ int  pvt_shard_commit(pvt_ctx* ctx, const void* packages);
  * array pointers are device pointers, exactly as for pvt_place() (mt_state in host memory);
  * each round is placed exactly as pvt_place() would place it. Synchronises before returning.
  * Returns PVT_EUNSUPPORTED if a round exceeds the limits (use pvt_place for it).
+ * A cost_aware round of more than 32 zones, and every round of a mixed-policy batch that holds
+ * a round of more than 32 zones, is resident up to PVT_RESIDENT_WIDE_MAX_HOSTS hosts (the wide
+ * kernels hold at most 8 hosts per lane); pvt_place and pvt_place_host run larger ones on the
+ * windowed engine.
  *
  * pvt_set_resident(ctx, max_hosts): pvt_place() runs rounds with n_hosts <= max_hosts (and
  * n_tasks within the limit) as a batch of one; 0 disables it (the windowed score/commit path
  * runs every round). Default PVT_RESIDENT_MAX_HOSTS. Results are identical either way.
  */
 #define PVT_RESIDENT_MAX_HOSTS 4096
+#define PVT_RESIDENT_WIDE_MAX_HOSTS 2048
 #define PVT_RESIDENT_MAX_TASKS 4096
 int  pvt_place_batch(pvt_ctx* ctx, const pvt_round* rounds, int32_t n_rounds);
 /* pvt_place_batch with the rounds' MT19937 states resident on the device: mt_dev[n_rounds][625]

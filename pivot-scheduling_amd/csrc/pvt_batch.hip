@@ -119,9 +119,11 @@ struct ResLds {
   }
 };
 
+#ifndef PVT_RESIDENT_WIDE_TU
 size_t resident_lds_bytes(int Zb, int Tpad, const ResidentSwitches& sw) {
   return (size_t)ResLds(Zb, Tpad, sw).total;
 }
+#endif
 
 __device__ __forceinline__ uint64_t dbits(double x) { return (uint64_t)__double_as_longlong(x); }
 
@@ -867,7 +869,10 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
 // One round on this workgroup (R: its descriptor, in SGPRs). The MT19937 state of an
 // opportunistic round is read and written through R.mt_state (a device pointer in every
 // resident path: pvt_place_batch's upload, pvt_place_batch_mt's rows, pvt_place_host's stage).
-template <int MODE, int WAVES, int HPL>
+// WIDE (batches with a round of more than ZMAX zones, resident_wide_kernel): no zone tables in
+// LDS (A.Zb = 0) -- an anchor's row is read from the round's cost and bw tables in global memory
+// with the same one add per entry -- and no one-wave walks (their zone masks are 32 bits).
+template <int MODE, int WAVES, int HPL, bool WIDE = false>
 __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_round& R) {
   constexpr int NT = WAVES * WAVE;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -884,7 +889,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   const bool has_groups = (MODE != OPP) && R.task_group && R.group_anchor;
   const bool keyed = (MODE == CA_FF) && R.sort_hosts;
 
-  if (CA)
+  if (CA && !WIDE)
     for (int i = tid; i < Z * Z; i += NT) {
       const int a = i / Z, z = i - a * Z;
       csum[i] = G(R.cost)[a * Z + z] + G(R.cost)[z * Z + a];
@@ -935,7 +940,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   // ca_bf 0.743 vs 0.779 ms at config 4); this path takes over where it stops, on the walked
   // capacities.
   int p_start = 0;
-  if (MODE == CA_BF && A.sw.walk_ca_bf && H <= RW_MAXH && T > 0 && !R.rt_bw) {
+  if (!WIDE && MODE == CA_BF && A.sw.walk_ca_bf && H <= RW_MAXH && T > 0 && !R.rt_bw) {
 #ifdef PVT_STAMPS
     const uint64_t tw0 = rstamp();
 #endif
@@ -961,7 +966,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   }
   // first fit by index (vbp first-fit; cost_aware first-fit without sort_hosts): the whole round
   // walked by one wave (resident_walk_ff), this path then only writes the results
-  if ((MODE == VBP_FF || (MODE == CA_FF && !keyed)) && A.sw.walk_ff && H <= RW_MAXH && T > 0) {
+  if (!WIDE && (MODE == VBP_FF || (MODE == CA_FF && !keyed)) && A.sw.walk_ff && H <= RW_MAXH && T > 0) {
 #ifdef PVT_STAMPS
     const uint64_t tw0 = rstamp();
 #endif
@@ -1199,6 +1204,12 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           cur_bgrp = grp_q;
 #pragma unroll
           for (int j = 0; j < HPL; j++) {
+            if constexpr (WIDE) {
+              cc[j] = G(R.cost)[anc * Z + zz[j]] + G(R.cost)[zz[j] * Z + anc];
+              bb[j] = rt ? (h0 + j < H ? G(R.rt_bw)[(size_t)grp_q * H + h0 + j] : 1.0)
+                         : G(R.bw)[anc * Z + zz[j]] + G(R.bw)[zz[j] * Z + anc];
+              continue;
+            }
             cc[j] = csum[anc * Z + zz[j]];
             bb[j] = rt ? (h0 + j < H ? G(R.rt_bw)[(size_t)grp_q * H + h0 + j] : 1.0) : bsum[anc * Z + zz[j]];
           }
@@ -1574,6 +1585,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   }
 }
 
+#ifndef PVT_RESIDENT_WIDE_TU
 template <int MODE, int WAVES, int HPL>
 __global__ __launch_bounds__(WAVES * WAVE) void resident_kernel(ResidentArgs A) {
   const pvt_round R = reinterpret_cast<const pvt_round*>(A.rounds)[blockIdx.x];   // SGPRs
@@ -1674,6 +1686,8 @@ void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const Resi
   }
 }
 
+#endif  // !PVT_RESIDENT_WIDE_TU
+
 // ---- fused host batch (pvt_place_host_batch): ONE launch per call ----------------------------
 // The staged path took six dependent launches per call (stage upload, anchor wave and block
 // kernels, grouping, resident placement, result download: ~5 us of launch gap each on MI355X,
@@ -1706,24 +1720,27 @@ __device__ __forceinline__ void block_copy2(char* dst, const char* src, int64_t 
   }
 }
 
-template <int MODE, int HPL>
+template <int MODE, int HPL, bool WIDE>
 __device__ __forceinline__ void fused_place(const FusedArgs& F, const pvt_round& R) {
   if (MODE == RES_MIXED) {
     switch (R.mode) {
-      case CA_FF: resident_round<CA_FF, 4, HPL>(F.ra, R); break;
-      case CA_BF: resident_round<CA_BF, 4, HPL>(F.ra, R); break;
-      case OPP: resident_round<OPP, 4, HPL>(F.ra, R); break;
-      case VBP_FF: resident_round<VBP_FF, 4, HPL>(F.ra, R); break;
-      case VBP_BF: resident_round<VBP_BF, 4, HPL>(F.ra, R); break;
+      case CA_FF: resident_round<CA_FF, 4, HPL, WIDE>(F.ra, R); break;
+      case CA_BF: resident_round<CA_BF, 4, HPL, WIDE>(F.ra, R); break;
+      case OPP: resident_round<OPP, 4, HPL, WIDE>(F.ra, R); break;
+      case VBP_FF: resident_round<VBP_FF, 4, HPL, WIDE>(F.ra, R); break;
+      case VBP_BF: resident_round<VBP_BF, 4, HPL, WIDE>(F.ra, R); break;
       default: break;
     }
   } else {
-    resident_round<MODE, 4, HPL>(F.ra, R);
+    resident_round<MODE, 4, HPL, WIDE>(F.ra, R);
   }
 }
 
-template <int MODE, int HPL>
+// HPLP: the hosts per lane; negative: the wide instance (resident_round's WIDE) with -HPLP
+template <int MODE, int HPLP>
 __global__ __launch_bounds__(4 * WAVE) void resident_fused_kernel(FusedArgs F) {
+  constexpr bool WIDE = HPLP < 0;
+  constexpr int HPL = WIDE ? -HPLP : HPLP;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const FusedRound fr = reinterpret_cast<const FusedRound*>(F.hmap + F.o_rounds)[blockIdx.x];
   constexpr bool ITEMS = MODE == RES_MIXED || MODE == CA_FF || MODE == CA_BF;
@@ -1764,7 +1781,7 @@ __global__ __launch_bounds__(4 * WAVE) void resident_fused_kernel(FusedArgs F) {
     FSTAMP(2);
   }
   const pvt_round R = *reinterpret_cast<const pvt_round*>(F.dev + fr.desc);   // (n_groups set)
-  fused_place<MODE, HPL>(F, R);
+  fused_place<MODE, HPL, WIDE>(F, R);
   __syncthreads();
   FSTAMP(3);
   block_copy2<16>(const_cast<char*>(F.hmap), F.dev, fr.out_lo, fr.out_hi - fr.out_lo, 0, 0);
@@ -1772,6 +1789,8 @@ __global__ __launch_bounds__(4 * WAVE) void resident_fused_kernel(FusedArgs F) {
   FSTAMP(4);
 #undef FSTAMP
 }
+
+#ifndef PVT_RESIDENT_WIDE_TU
 
 size_t fused_pre_lds_bytes() {
   size_t b = 4 * ANC_WLDS * sizeof(uint64_t);
@@ -1847,7 +1866,84 @@ hipError_t resident_init_attrs() {
   if ((r = attrs_fused<VBP_FF>(flds)) != hipSuccess) e = r;
   if ((r = attrs_fused<VBP_BF>(flds)) != hipSuccess) e = r;
   if ((r = attrs_fused<RES_MIXED>(flds)) != hipSuccess) e = r;
+  if ((r = resident_wide_init_attrs()) != hipSuccess) e = r;
   return e;
 }
+
+#else  // PVT_RESIDENT_WIDE_TU: the wide kernels, compiled as a unit of their own (pvt_batch_wide.hip)
+
+// Batches with a round of more than ZMAX zones whose policies read the zone tables: cost_aware
+// first-fit, cost_aware best-fit, or mixed policies (RES_MIXED). Four waves, at most
+// RES_WIDE_MAX_HPL hosts per lane. Batches of the other policies run resident_kernel as it is
+// (they never touch the tables; the host lays their LDS out with Zb = 0).
+template <int MODE, int HPL>
+__global__ __launch_bounds__(4 * WAVE) void resident_wide_kernel(ResidentArgs A) {
+  const pvt_round R = reinterpret_cast<const pvt_round*>(A.rounds)[blockIdx.x];   // SGPRs
+  if (MODE == RES_MIXED) {
+    switch (R.mode) {
+      case CA_FF: resident_round<CA_FF, 4, HPL, true>(A, R); break;
+      case CA_BF: resident_round<CA_BF, 4, HPL, true>(A, R); break;
+      case OPP: resident_round<OPP, 4, HPL, true>(A, R); break;
+      case VBP_FF: resident_round<VBP_FF, 4, HPL, true>(A, R); break;
+      case VBP_BF: resident_round<VBP_BF, 4, HPL, true>(A, R); break;
+      default: break;
+    }
+  } else {
+    resident_round<MODE, 4, HPL, true>(A, R);
+  }
+}
+
+#define PVT_WIDE_HPL(KERNEL, M, S, ARG)                                             \
+  switch (hpl) {                                                                    \
+    case 1: PVT_LAUNCH((KERNEL<M, S 1>), grid, block, lds, st, ARG); break;          \
+    case 2: PVT_LAUNCH((KERNEL<M, S 2>), grid, block, lds, st, ARG); break;          \
+    case 4: PVT_LAUNCH((KERNEL<M, S 4>), grid, block, lds, st, ARG); break;          \
+    default: PVT_LAUNCH((KERNEL<M, S 8>), grid, block, lds, st, ARG); break;         \
+  }
+void launch_resident_wide(int mode, int hpl, int n, size_t lds, const ResidentArgs& a, hipStream_t st) {
+  const dim3 grid(n), block(4 * WAVE);
+  switch (mode) {
+    case CA_FF: PVT_WIDE_HPL(resident_wide_kernel, CA_FF, +, a) break;
+    case CA_BF: PVT_WIDE_HPL(resident_wide_kernel, CA_BF, +, a) break;
+    default: PVT_WIDE_HPL(resident_wide_kernel, RES_MIXED, +, a) break;
+  }
+}
+void launch_fused_wide(int mode, int hpl, int n, size_t lds, const FusedArgs& F, hipStream_t st) {
+  const dim3 grid(n), block(4 * WAVE);
+  switch (mode) {
+    case CA_FF: PVT_WIDE_HPL(resident_fused_kernel, CA_FF, -, F) break;
+    case CA_BF: PVT_WIDE_HPL(resident_fused_kernel, CA_BF, -, F) break;
+    default: PVT_WIDE_HPL(resident_fused_kernel, RES_MIXED, -, F) break;
+  }
+}
+#undef PVT_WIDE_HPL
+
+template <int MODE>
+static hipError_t attrs_wide(int lds) {
+  hipError_t e = hipSuccess, r;
+#define PVT_WIDE_ATTR(HPL)                                                                       \
+  r = hipFuncSetAttribute((const void*)resident_wide_kernel<MODE, HPL>,                          \
+                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);                      \
+  if (r != hipSuccess) e = r;                                                                    \
+  r = hipFuncSetAttribute((const void*)resident_fused_kernel<MODE, -HPL>,                        \
+                          hipFuncAttributeMaxDynamicSharedMemorySize, lds);                      \
+  if (r != hipSuccess) e = r;
+  PVT_WIDE_ATTR(1) PVT_WIDE_ATTR(2) PVT_WIDE_ATTR(4) PVT_WIDE_ATTR(8)
+#undef PVT_WIDE_ATTR
+  return e;
+}
+
+hipError_t resident_wide_init_attrs() {
+  // (no tables, no walk region: the sort keys of RES_MAX_TASKS tasks are the largest use)
+  const int lds = (int)std::max((size_t)ResLds(0, RES_MAX_TASKS, ResidentSwitches{}).total,
+                                fused_pre_lds_bytes());
+  hipError_t e = hipSuccess, r;
+  if ((r = attrs_wide<CA_FF>(lds)) != hipSuccess) e = r;
+  if ((r = attrs_wide<CA_BF>(lds)) != hipSuccess) e = r;
+  if ((r = attrs_wide<RES_MIXED>(lds)) != hipSuccess) e = r;
+  return e;
+}
+
+#endif  // PVT_RESIDENT_WIDE_TU
 
 }  // namespace pvt

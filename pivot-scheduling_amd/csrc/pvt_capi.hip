@@ -133,6 +133,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
       hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming) != hipSuccess ||
       hipEventCreateWithFlags(&ctx->ev_rstage, hipEventDisableTiming) != hipSuccess ||
       init_kernel_attrs() != hipSuccess || pvt::opp_init_attrs() != hipSuccess ||
+      score_init_attrs() != hipSuccess ||
       resident_init_attrs() != hipSuccess || lwalk_init_attrs() != hipSuccess ||
       hipHostMalloc((void**)&ctx->next_host, sizeof(int32_t) * 4) != hipSuccess ||
       hipHostMalloc((void**)&ctx->flag_host, sizeof(int32_t) * 16, hipHostMallocCoherent) != hipSuccess ||
@@ -332,13 +333,17 @@ extern "C" int pvt_debug_score_counts(pvt_ctx* ctx, uint64_t* out, int n, int re
   return pvt::score_diag(out, n, reset);
 }
 
+static_assert(PVT_MAX_ZONES == pvt::ZWIDE, "the public zone bound is the wide kernels' bound");
+extern "C" int pvt_max_zones(void) { return PVT_MAX_ZONES; }
+
 extern "C" const char* pvt_last_error(pvt_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int pvt::check_round(pvt_ctx* ctx, const pvt_round* r) {
   if (!r) return fail(ctx, PVT_EINVAL, "null round");
   if (r->reserved != 0) return fail(ctx, PVT_EINVAL, "reserved must be 0");
-  if (r->n_hosts < 1 || r->n_tasks < 0 || r->n_zones < 1 || r->n_zones > ZMAX)
-    return fail(ctx, PVT_EINVAL, "bad sizes H=%d T=%d Z=%d", r->n_hosts, r->n_tasks, r->n_zones);
+  if (r->n_hosts < 1 || r->n_tasks < 0 || r->n_zones < 1 || r->n_zones > PVT_MAX_ZONES)
+    return fail(ctx, PVT_EINVAL, "bad sizes H=%d T=%d Z=%d (1 <= Z <= PVT_MAX_ZONES = %d)", r->n_hosts,
+                r->n_tasks, r->n_zones, PVT_MAX_ZONES);
   if (r->mode < PVT_CA_FF || r->mode > PVT_VBP_BF) return fail(ctx, PVT_EINVAL, "bad mode %d", r->mode);
   if (!r->avail || !r->zone) return fail(ctx, PVT_EINVAL, "null host array");
   if (r->n_tasks > 0 && (!r->dem || !r->order || !r->placement))

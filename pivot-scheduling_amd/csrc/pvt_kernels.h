@@ -42,7 +42,10 @@ extern thread_local TimedEvents g_timed;
 
 constexpr int WAVE = 64;
 constexpr int KL = 64;           // candidate list length per task (one entry per lane)
-constexpr int ZMAX = 32;         // zones supported (locality.yml has 31)
+constexpr int ZMAX = 32;         // zones of the fast paths: zone tables in LDS, 32-bit zone masks
+                                 //   (frontier walks, epochs, resident walks; locality.yml has 31)
+constexpr int ZWIDE = 512;       // zones of a round (PVT_MAX_ZONES): above ZMAX the wide kernels
+                                 //   read the sum tables from global memory
 constexpr int TW = 4;            // tasks per wave in the score kernel
 constexpr int WPB = 4;           // waves per score-kernel block
 constexpr int MAX_WINDOW = 1024; // tasks per window (bounded by the commit kernel's LDS)
@@ -454,7 +457,8 @@ void launch_band_score(const BandArgs& a, hipStream_t st);
 // rdem = the rows' demands, *nrep = rows (nt <= MAX_WINDOW)
 void launch_band_runs(const double* dem, int T, int32_t* run, double* rdem, hipStream_t st);
 
-int score_tasks_per_wave(int mode, int hosts, int force = 0);
+int score_tasks_per_wave(int mode, int hosts, int force = 0, int zones = 0);
+hipError_t score_init_attrs();
 int score_diag(uint64_t* out, int n, int reset);   // PVT_DIAG builds; else PVT_EUNSUPPORTED
 void launch_score(int mode, const ScoreArgs& a, hipStream_t st);
 void launch_merge(const MergeArgs& a, hipStream_t st);
@@ -551,6 +555,13 @@ void resident_shape(int maxH, int* waves, int* hpl);
 void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const ResidentArgs& a,
                      hipStream_t st);
 hipError_t resident_init_attrs();
+// Batches with a round of more than ZMAX zones (pvt_batch_wide.hip): mode CA_FF, CA_BF or
+// RES_MIXED -- batches of one other policy run launch_resident with a.Zb = 0. Four waves, hpl <=
+// RES_WIDE_MAX_HPL (16 hosts per lane would spill registers), a.Zb = 0 and no walk switches.
+constexpr int RES_WIDE_MAX_HPL = 8;
+constexpr int RES_WIDE_MAX_HOSTS = 4 * WAVE * RES_WIDE_MAX_HPL;   // 2048
+void launch_resident_wide(int mode, int hpl, int n, size_t lds, const ResidentArgs& a, hipStream_t st);
+hipError_t resident_wide_init_attrs();
 
 // The fused host batch (pvt_place_host_batch): per round (one workgroup of four waves), its byte
 // ranges of the pinned stage -- the same offsets in the mapped host copy and the device copy --
@@ -569,6 +580,7 @@ struct FusedArgs {
 };
 size_t fused_pre_lds_bytes();   // LDS of the anchor and grouping phases
 void launch_fused(int mode, int hpl, int n, size_t lds, const FusedArgs& F, hipStream_t st);
+void launch_fused_wide(int mode, int hpl, int n, size_t lds, const FusedArgs& F, hipStream_t st);
 size_t commit_lds_bytes();
 hipError_t init_kernel_attrs();
 // grouped processing order: group counts (cnt[G] = out-of-range ids), scatter by group, one

@@ -34,10 +34,16 @@ __device__ unsigned long long g_score_diag[8];
 // list per task in registers. blockIdx % S picks the segment, so with S = 8 the blocks of one
 // segment share an XCD (round-robin dispatch) and its L2 holds that slice of the host table.
 // ------------------------------------------------------------------------------------------
-template <int MODE, int TW>
+// TWP < 0: the wide instance for cost_aware best-fit rounds of more than ZMAX zones, -TWP tasks
+// per wave. Its per-zone rows live in dynamic LDS, A.Z doubles each (score_wide_lds_bytes), and
+// are filled and refreshed 64 zones at a time; everything else is the same code. The per-zone
+// limits and radii only prune, and the wide rows hold the same values the narrow ones would.
+template <int MODE, int TWP>
 __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
+  constexpr bool WIDE = TWP < 0;
+  constexpr int TW = WIDE ? -TWP : TWP;
   constexpr bool STRICT = (MODE != CA_BF);
-  constexpr int ZL = (MODE == CA_BF) ? ZMAX : 1;
+  constexpr int ZL = (MODE == CA_BF && !WIDE) ? ZMAX : 1;
   __shared__ double s_lim[WPB][TW][ZL];
   __shared__ double s_rad[WPB][TW][ZL];
   __shared__ double s_c[WPB][TW][ZL];
@@ -45,6 +51,18 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
   __shared__ uint64_t s_m1[WPB][KL], s_m2[WPB][KL];   // list_merge staging, per wave
 
   const int lane = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // wide: this wave's rows in dynamic LDS, [lim | rad | c | b][WPB][TW][Z], row k at [k * A.Z]
+  double *w_lim = nullptr, *w_rad = nullptr, *w_c = nullptr, *w_b = nullptr;
+  if constexpr (WIDE) {
+    extern __shared__ __attribute__((aligned(16))) double s_wide[];
+    const int arr = WPB * TW * A.Z;
+    w_lim = s_wide + wave * TW * A.Z;
+    w_rad = w_lim + arr;
+    w_c = w_rad + arr;
+    w_b = w_c + arr;
+  }
+// zone z's entry of task k's row
+#define ZROW(name, k, z) (*(WIDE ? &w_##name[(k) * A.Z + (z)] : &s_##name[wave][k][z]))
   const int seg = blockIdx.x % A.S, tile = blockIdx.x / A.S;
   const int t0 = (tile * WPB + wave) * TW;
   if (t0 >= A.nt) return;
@@ -79,6 +97,14 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
     rb[k] = (rt && k < nt) ? A.rtb + (size_t)A.grp[t0 + k] * A.H : A.rtb;
     if (MODE == CA_BF) {
       const int a = (k < nt) ? A.anc[t0 + k] : 0;
+      if constexpr (WIDE) {
+        for (int z = lane; z < A.Z; z += WAVE) {
+          ZROW(c, k, z) = A.csum[a * A.Z + z];
+          ZROW(b, k, z) = A.bsum[a * A.Z + z];
+          ZROW(lim, k, z) = DINF;
+          ZROW(rad, k, z) = rd[k];
+        }
+      } else
       if (lane < A.Z) {
         s_c[wave][k][lane] = A.csum[a * A.Z + lane];
         s_b[wave][k][lane] = A.bsum[a * A.Z + lane];
@@ -132,7 +158,7 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
       if (MODE == CA_FF) {
         pre[k] = ok && lexless(key, 0u, h, ts[k], tt[k], ti[k]);
       } else {
-        const double r = (MODE == CA_BF) ? s_rad[wave][k][z] : rd[k];
+        const double r = (MODE == CA_BF) ? ZROW(rad, k, z) : rd[k];
         pre[k] = ok && (__builtin_fabs(a1 - d1[k]) <= r);
       }
       any |= pre[k];
@@ -156,7 +182,7 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
         pass = fit;
       } else {
         s2 = norm2_seq(a0 - d0[k], a1 - d1[k], a2 - d2[k], a3 - d3[k]);
-        const double lm = (MODE == CA_BF) ? s_lim[wave][k][z] : lim[k];
+        const double lm = (MODE == CA_BF) ? ZROW(lim, k, z) : lim[k];
         pass = fit && (s2 <= lm);
       }
       uint64_t pm = __ballot(pass);
@@ -171,7 +197,7 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
             sc = key;
           } else if (MODE == CA_BF) {
             const double r = __builtin_sqrt(s2);
-            sc = (s_c[wave][k][z] * r) / (rt ? rb[k][h] : s_b[wave][k][z]);
+            sc = (ZROW(c, k, z) * r) / (rt ? rb[k][h] : ZROW(b, k, z));
           } else {
             sc = __builtin_sqrt(s2);
             tbv = tbh;
@@ -194,6 +220,13 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
           ti[k] = readlane_i(li[k], KL - 1);
 
           if (MODE == CA_BF && !rt) {
+            if constexpr (WIDE) {
+              for (int z = lane; z < A.Z; z += WAVE) {
+                const double lm2 = ca_lim(ts[k], ZROW(c, k, z), ZROW(b, k, z));
+                ZROW(lim, k, z) = lm2;
+                ZROW(rad, k, z) = rad(lm2);
+              }
+            } else
             if (lane < A.Z) {
               const double lm2 = ca_lim(ts[k], s_c[wave][k][lane], s_b[wave][k][lane]);
               s_lim[wave][k][lane] = lm2;
@@ -226,6 +259,18 @@ __global__ __launch_bounds__(256) void score_kernel(ScoreArgs A) {
       if (lane == 0) A.seg_feas[row] = filled == KL ? KL + 1 : filled;
     }
   }
+#undef ZROW
+}
+
+// The wide instance runs two tasks per wave, so a block's rows are 4 arrays x 4 waves x 2 tasks x
+// Z doubles: 128 KiB at 512 zones, one block per CU.
+constexpr int TW_WIDE = 2;
+static size_t score_wide_lds_bytes(int Z) { return sizeof(double) * 4 * WPB * TW_WIDE * (size_t)Z; }
+static_assert(sizeof(double) * 4 * WPB * TW_WIDE * ZWIDE + 2 * sizeof(uint64_t) * WPB * KL +
+                      4 * sizeof(double) * WPB * TW_WIDE <= 160 * 1024, "wide score rows exceed a CU's LDS");
+hipError_t score_init_attrs() {
+  return hipFuncSetAttribute((const void*)score_kernel<CA_BF, -TW_WIDE>,
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)score_wide_lds_bytes(ZWIDE));
 }
 
 // Tasks per wave: vbp best-fit lists keep improving while a segment streams, so each block costs
@@ -251,7 +296,8 @@ int score_diag(uint64_t* out, int n, int reset) {
 #endif
 }
 
-int score_tasks_per_wave(int mode, int hosts, int force) {
+int score_tasks_per_wave(int mode, int hosts, int force, int zones) {
+  if (mode == CA_BF && zones > ZMAX) return TW_WIDE;
   if (force == 2 || force == 4) return force;   // pvt_set_score_tw: both instances stay tested
   if (mode == VBP_BF) return 2;
   if (mode == CA_BF && hosts < (1 << 18)) return 2;
@@ -265,9 +311,13 @@ static void launch_score_tw(int tw, dim3 grid, dim3 block, const ScoreArgs& a, h
 }
 
 void launch_score(int mode, const ScoreArgs& a, hipStream_t st) {
-  const int tw = score_tasks_per_wave(mode, a.h_hi - a.h_lo, a.tw);
+  const int tw = score_tasks_per_wave(mode, a.h_hi - a.h_lo, a.tw, a.Z);
   const int tiles = (a.nt + WPB * tw - 1) / (WPB * tw);
   dim3 grid(tiles * a.S), block(WPB * WAVE);
+  if (mode == CA_BF && a.Z > ZMAX) {
+    PVT_LAUNCH((score_kernel<CA_BF, -TW_WIDE>), grid, block, score_wide_lds_bytes(a.Z), st, a);
+    return;
+  }
   switch (mode) {
     case CA_FF: launch_score_tw<CA_FF>(tw, grid, block, a, st); break;
     case CA_BF: launch_score_tw<CA_BF>(tw, grid, block, a, st); break;

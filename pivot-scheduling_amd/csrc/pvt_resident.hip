@@ -7,8 +7,11 @@
 
 // ---------------------------------------------------------------- resident rounds / batches
 bool pvt::resident_fits(const pvt_round* r, int max_hosts) {
-  return r->n_hosts <= std::min(max_hosts, (int)PVT_RESIDENT_MAX_HOSTS) &&
-         r->n_tasks <= PVT_RESIDENT_MAX_TASKS;
+  // (a cost_aware round of more than ZMAX zones runs the wide kernels, which hold at most
+  // RES_WIDE_MAX_HPL hosts per lane; so does every round of a mixed batch with one: plan_check)
+  const bool ca = r->mode == PVT_CA_FF || r->mode == PVT_CA_BF;
+  const int cap = ca && r->n_zones > ZMAX ? RES_WIDE_MAX_HOSTS : (int)PVT_RESIDENT_MAX_HOSTS;
+  return r->n_hosts <= std::min(max_hosts, cap) && r->n_tasks <= PVT_RESIDENT_MAX_TASKS;
 }
 
 template <class T>
@@ -32,6 +35,8 @@ struct ResidentPlan {
   int n = 0, waves = 4, hpl = 1;
   int Zb = 1, Tpad = 64;          // LDS zone-table stride, sort network size (a power of two)
   ResidentSwitches sw;
+  bool wide_kernel = false;       // a round of more than ZMAX zones (no zone tables in LDS: Zb = 0)
+                                  //   and a policy that reads them, or mixed policies: the wide kernels
   size_t lds = 0;
   double cand = 0.0, bytes = 0.0;
 };
@@ -43,8 +48,11 @@ static ResidentPlan plan_resident(const pvt_ctx* ctx, const pvt_round* rounds, c
   ResidentPlan plan;
   plan.n = n;
   int maxH = 1, maxT = 1;
+  bool tables = false, mixed = false;   // a cost_aware round; rounds of different policies
   for (int k = 0; k < n; k++) {
     const pvt_round& r = rounds[idx ? idx[k] : k];
+    tables |= r.mode == PVT_CA_FF || r.mode == PVT_CA_BF;
+    mixed |= r.mode != rounds[idx ? idx[0] : 0].mode;
     maxH = std::max(maxH, r.n_hosts);
     maxT = std::max(maxT, r.n_tasks);
     plan.Zb = std::max(plan.Zb, r.n_zones);
@@ -56,8 +64,26 @@ static ResidentPlan plan_resident(const pvt_ctx* ctx, const pvt_round* rounds, c
   resident_shape(maxH, &plan.waves, &plan.hpl);
   while (plan.Tpad < maxT) plan.Tpad <<= 1;
   plan.sw = resident_switches(ctx->rwalk, maxH);
+  if (plan.Zb > ZMAX) {
+    plan.Zb = 0;
+    plan.wide_kernel = tables || mixed;
+    if (plan.wide_kernel) {       // four waves, no one-wave walks (32-bit zone masks)
+      plan.waves = 4;
+      resident_shape(maxH, &plan.waves, &plan.hpl);
+      plan.sw.walk_ca_bf = plan.sw.walk_ff = plan.sw.walk_rotate = plan.sw.walk_bulk = 0;
+    }
+  }
   plan.lds = std::max(resident_lds_bytes(plan.Zb, plan.Tpad, plan.sw), min_lds);
   return plan;
+}
+
+// A wide batch on the wide kernels holds at most RES_WIDE_MAX_HPL hosts per lane: every round of
+// it, the narrow ones too.
+static int plan_check(pvt_ctx* ctx, const ResidentPlan& plan) {
+  if (plan.wide_kernel && plan.hpl > RES_WIDE_MAX_HPL)
+    return fail(ctx, PVT_EUNSUPPORTED, "a batch with a round of more than %d zones takes rounds of at most "
+                "%d hosts: place the larger rounds in a batch of their own", ZMAX, RES_WIDE_MAX_HOSTS);
+  return PVT_OK;
 }
 
 static ResidentArgs plan_args(const pvt_ctx* ctx, const ResidentPlan& plan, const void* desc, uint32_t* mt) {
@@ -66,10 +92,15 @@ static ResidentArgs plan_args(const pvt_ctx* ctx, const ResidentPlan& plan, cons
 
 // mode: the rounds' policy, or RES_MIXED; desc: their descriptors on the device
 static int run_resident(pvt_ctx* ctx, const ResidentPlan& plan, int mode, const void* desc, uint32_t* mt) {
+  int rc = plan_check(ctx, plan);
+  if (rc) return rc;
   {
     Scope sc(ctx, PVT_K_SCORE, plan.cand, plan.bytes, nullptr, "resident_kernel");
-    launch_resident(mode, plan.waves, plan.hpl, plan.n, plan.lds, plan_args(ctx, plan, desc, mt),
-                    ctx->stream);
+    if (plan.wide_kernel)
+      launch_resident_wide(mode, plan.hpl, plan.n, plan.lds, plan_args(ctx, plan, desc, mt), ctx->stream);
+    else
+      launch_resident(mode, plan.waves, plan.hpl, plan.n, plan.lds, plan_args(ctx, plan, desc, mt),
+                      ctx->stream);
   }
   HIPCHK(hipGetLastError());
   ctx->windows = plan.n;
@@ -89,8 +120,9 @@ int pvt::place_resident(pvt_ctx* ctx, const pvt_round* rounds, int n, const void
     if (rc) return rc;
     if (r->mode != mode) return fail(ctx, PVT_EINVAL, "batch round %d: mode %d != %d", i, r->mode, mode);
     if (!resident_fits(r, PVT_RESIDENT_MAX_HOSTS))
-      return fail(ctx, PVT_EUNSUPPORTED, "batch round %d: H=%d T=%d exceeds the resident limits (%d, %d)",
-                  i, r->n_hosts, r->n_tasks, PVT_RESIDENT_MAX_HOSTS, PVT_RESIDENT_MAX_TASKS);
+      return fail(ctx, PVT_EUNSUPPORTED, "batch round %d: H=%d T=%d exceeds the resident limits (%d, %d; "
+                  "%d hosts with more than %d zones)", i, r->n_hosts, r->n_tasks, PVT_RESIDENT_MAX_HOSTS,
+                  PVT_RESIDENT_MAX_TASKS, RES_WIDE_MAX_HOSTS, ZMAX);
   }
   HIPCHK(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -197,7 +229,9 @@ static int check_host_round(pvt_ctx* ctx, const pvt_round* r, pvt_ca_items* it, 
       return fail(ctx, PVT_EUNSUPPORTED, "fused grouping limits: T=%d (max %d), %d storages + %d "
                   "applications (max %d, at least one storage)", T, GRP_MAX_TASKS, it->n_storage,
                   it->n_apps, GRP_MAX_KEYS);
-    if (Z < 1 || Z > ZMAX) return fail(ctx, PVT_EINVAL, "bad sizes H=%d T=%d Z=%d", r->n_hosts, T, Z);
+    if (Z < 1 || Z > PVT_MAX_ZONES)
+      return fail(ctx, PVT_EINVAL, "bad sizes H=%d T=%d Z=%d (1 <= Z <= PVT_MAX_ZONES = %d)", r->n_hosts, T, Z,
+                  PVT_MAX_ZONES);
     for (int k = 0; k < it->n_storage; k++)
       if (it->storage_zone[k] < 0 || it->storage_zone[k] >= Z)
         return fail(ctx, PVT_EINVAL, "storage %d: zone %d outside [0, %d)", k, it->storage_zone[k], Z);
@@ -495,11 +529,14 @@ static int place_host_fused(pvt_ctx* ctx, const HostBatch& B) {
       if (B.live[j] == B.withit[k]) fr[j].items = (int32_t)k;
   const ResidentPlan plan = plan_resident(ctx, B.rounds, B.live.data(), (int)B.live.size(), 4,
                                           B.withit.empty() ? 0 : fused_pre_lds_bytes());
+  int rc = plan_check(ctx, plan);
+  if (rc) return rc;
   FusedArgs F{static_cast<const char*>(ctx->hst_map), static_cast<char*>(ctx->hdev.p),
               (int64_t)B.o_fr, (int64_t)B.o_ka, (int64_t)B.o_kg, plan_args(ctx, plan, nullptr, nullptr)};
   {
     Scope sc(ctx, PVT_K_SCORE, plan.cand, plan.bytes, nullptr, "resident_fused_kernel");
-    launch_fused(B.mode, plan.hpl, plan.n, plan.lds, F, ctx->stream);
+    if (plan.wide_kernel) launch_fused_wide(B.mode, plan.hpl, plan.n, plan.lds, F, ctx->stream);
+    else launch_fused(B.mode, plan.hpl, plan.n, plan.lds, F, ctx->stream);
   }
   HIPCHK(hipGetLastError());
   ctx->windows = plan.n;

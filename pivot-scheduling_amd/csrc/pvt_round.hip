@@ -20,8 +20,8 @@ static constexpr size_t SEG_ENTRIES_MAX = (size_t)MAX_WINDOW * MAX_SEG * KL;
 // about KL * (1 + ln(H / (S * KL))) serial insertions per segment, S times per task. Fewer,
 // longer segments halve those insertions at 16 (measured: 29.7 -> 26.2 ms of score per
 // 1M x 10k round); cost_aware's zero-cost zone fills its lists at once and wants the waves.
-static int choose_segments(int H, int nt, int mode, int force_tw, bool epoch, int force_S) {
-  const int tw = score_tasks_per_wave(mode, H, force_tw);
+static int choose_segments(int H, int nt, int mode, int force_tw, bool epoch, int force_S, int Z) {
+  const int tw = score_tasks_per_wave(mode, H, force_tw, Z);
   const int task_waves = (nt + tw - 1) / tw;
   int S = (4096 + task_waves - 1) / task_waves;
   if (mode == PVT_VBP_BF) S = std::min(S, 16);
@@ -894,7 +894,7 @@ int pvt::window_lists(pvt_ctx* ctx, int t0, int nt, int lb, hipStream_t st) {
     Scope sc(ctx, PVT_K_MERGE, 0, 0, st, merge_kernel_name(ma));
     launch_merge(ma, st);
   } else {
-    const int S = choose_segments(Hl, nt, r->mode, ctx->score_tw, R.in_epoch, ctx->t_segments);
+    const int S = choose_segments(Hl, nt, r->mode, ctx->score_tw, R.in_epoch, ctx->t_segments, R.Z);
     ENSURE(ctx->seg, sizeof(SegEntry) * (size_t)nt * S * KL);
     ENSURE(ctx->seg_feas, sizeof(int32_t) * (size_t)nt * S);
     ScoreArgs sa{r->avail, r->zone, r->tiebreak, R.keyed ? P<double>(ctx->key) : nullptr,

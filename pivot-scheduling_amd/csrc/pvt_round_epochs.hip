@@ -38,6 +38,7 @@ int pvt::epoch_groups(pvt_ctx* ctx) {
   R.ega.clear();
   const int T = R.T;
   if (!ctx->epochs || r->mode != PVT_CA_BF || !r->task_group || r->n_groups < 2 || T < 2) return PVT_OK;
+  if (R.Z > ZMAX) return PVT_OK;              // wide rounds: pipelined windows (32-bit zone masks here)
   hipStream_t st = ctx->stream;
   int rc;
   std::vector<int> cnt(r->n_groups, 0);

@@ -64,6 +64,11 @@ constexpr int32_t H_DEAD = -2;            // hash value: touched, can no longer 
 constexpr int32_t H_PENDING = 0x7fffffff; // hash value before the walker writes it
 constexpr int SPIN_LIMIT = 1 << 24;       // bounded spins (x s_sleep 2 ~ seconds)
 constexpr int MAX_CHAIN_SEGS = 64;        // group segments per epoch chain
+// The walk's templates take MODEP = the policy (enum Mode), plus WALK_WIDE for a cost_aware
+// best-fit round of more than ZMAX zones: its zone sum tables do not fit the LDS (4 MB at 512
+// zones), so the two places that score a touched host read CommitArgs.csum / bsum in global
+// memory instead (cache-resident; the list entries carry their scores already).
+constexpr int WALK_WIDE = 8;
 
 // A scout's result: LOOK usable list entries in list order (untouched, or for first-fit
 // touched and fitting) and, for best-fit, the LOOK best live touched hosts; one 16-dword
@@ -209,13 +214,18 @@ __device__ __forceinline__ uint64_t ca_score_bits(double c, double s2, double bw
 
 // rtrow: the task's group row of the realtime bandwidth (cost_aware.py:79), or NULL. lim1: the
 // score bits a candidate must reach to matter (see ca_score_bits; ~0 = any).
-template <int MODE>
+template <int MODEP>
 __device__ __forceinline__ void bf_key(const WalkLDS& S, int Z, int anc, const double* rtrow,
                                        double a0, double a1, double a2, double a3, double d0,
                                        double d1, double d2, double d3, int32_t z, uint32_t tb,
-                                       int32_t id, uint64_t lim1, uint64_t& k1, uint64_t& k2) {
+                                       int32_t id, uint64_t lim1, uint64_t& k1, uint64_t& k2,
+                                       const double* gcsum = nullptr, const double* gbsum = nullptr) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   const double s2 = norm2_seq(a0 - d0, a1 - d1, a2 - d2, a3 - d3);
-  if (MODE == CA_BF)
+  if (MODE == CA_BF && WIDE)
+    k1 = ca_score_bits(gcsum[anc * Z + z], s2, rtrow ? rtrow[id] : gbsum[anc * Z + z], lim1);
+  else if (MODE == CA_BF)
     k1 = ca_score_bits(S.csum[anc * Z + z], s2, rtrow ? rtrow[id] : S.bsum[anc * Z + z], lim1);
   else
     k1 = (uint64_t)__double_as_longlong(__builtin_sqrt(s2));
@@ -229,9 +239,11 @@ __device__ __forceinline__ bool key_lt(uint64_t a1, uint64_t a2, uint64_t b1, ui
 // its list (ring, then the deep list in HBM) and, for best-fit, the LOOK best live touched hosts
 // that could still win; written to R.res. PART: 0 both, 1 the list entries only, 2 the touched
 // hosts only (best-fit tasks are scouted by two waves at once, one per part).
-template <int MODE, int PART>
+template <int MODEP, int PART>
 __device__ void scout(const CommitArgs& A, WalkLDS& S, RingSlot& R, int w, int k, int32_t rv,
                       const double* rtrow) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   constexpr bool STRICT = (MODE == CA_FF || MODE == VBP_BF);
   constexpr bool BEST = (MODE == CA_BF || MODE == VBP_BF);
   const int lane = lane_id();
@@ -353,9 +365,9 @@ __device__ void scout(const CommitArgs& A, WalkLDS& S, RingSlot& R, int w, int k
       const bool fit = (q < nlp) && fits<STRICT>(a0, a1, a2, a3, d0, d1, d2, d3);
       if (__ballot(fit) == 0) continue;
       uint64_t k1 = ~0ull, k2 = ~0ull;
-      bf_key<MODE>(S, A.Z, anc, rtrow, a0, a1, a2, a3, d0, d1, d2, d3, S.lz[qq],
+      bf_key<MODEP>(S, A.Z, anc, rtrow, a0, a1, a2, a3, d0, d1, d2, d3, S.lz[qq],
                    MODE == VBP_BF ? S.ltb[qq] : 0u, S.lid[qq], b1 < tk1[LOOK - 1] ? b1 : tk1[LOOK - 1],
-                   k1, k2);
+                   k1, k2, A.csum, A.bsum);
       uint64_t pm = __ballot(fit && key_lt(k1, k2, b1, b2) && key_lt(k1, k2, tk1[LOOK - 1], tk2[LOOK - 1]));
       // Many candidates (a zero-cost component's touched hosts all score 0): take the chunk's
       // LOOK smallest keys by wave-wide minima (DPP) instead of inserting them one by one.
@@ -436,8 +448,10 @@ __device__ constexpr int split_a() {
 static_assert(PVT_SPLIT_CA >= 0 && PVT_SPLIT_CA < PRODUCERS, "PVT_SPLIT_CA");
 static_assert(PVT_SPLIT_VBP >= 0 && PVT_SPLIT_VBP < PRODUCERS, "PVT_SPLIT_VBP");
 
-template <int MODE>
+template <int MODEP>
 __device__ void produce_touched(const CommitArgs& A, WalkLDS& S, int pb) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   const int lane = lane_id();
   for (int i = pb; i < A.nt; i += PRODUCERS - split_a<MODE>()) {
     const int w = widx(A, i);
@@ -456,7 +470,7 @@ __device__ void produce_touched(const CommitArgs& A, WalkLDS& S, int pb) {
     }
     cbarrier();
     __builtin_amdgcn_s_setprio(2);
-    scout<MODE, 2>(A, S, S.ring[slot], w, 0, rv,
+    scout<MODEP, 2>(A, S, S.ring[slot], w, 0, rv,
                    (MODE == CA_BF && A.rtb) ? A.rtb + (size_t)grp * A.H : nullptr);
     lds_drain();
     if (lane == 0) publish(&S.flagB[slot], i);
@@ -464,12 +478,14 @@ __device__ void produce_touched(const CommitArgs& A, WalkLDS& S, int pb) {
   }
 }
 
-template <int MODE>
+template <int MODEP>
 __device__ void produce(const CommitArgs& A, WalkLDS& S, int pw) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   constexpr bool BEST = (MODE == CA_BF || MODE == VBP_BF);
   constexpr int SA = split_a<MODE>();
   constexpr int NA = SA ? SA : PRODUCERS;
-  if (SA && pw >= SA) { produce_touched<MODE>(A, S, pw - SA); return; }
+  if (SA && pw >= SA) { produce_touched<MODEP>(A, S, pw - SA); return; }
   const int lane = lane_id();
   const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   for (int i = pw; i < A.nt; i += NA) {
@@ -544,7 +560,7 @@ __device__ void produce(const CommitArgs& A, WalkLDS& S, int pw) {
     // the scout is on the walk's critical path (the walker needs its result one task from now):
     // it outranks the other scouts' list loading, not the walker
     __builtin_amdgcn_s_setprio(2);
-    scout<MODE, SA ? 1 : 0>(A, S, R, w, k, rv,
+    scout<MODEP, SA ? 1 : 0>(A, S, R, w, k, rv,
                               (MODE == CA_BF && A.rtb) ? A.rtb + (size_t)grp * A.H : nullptr);
     lds_drain();
     if (lane == 0) publish(&S.flag[slot], i);
@@ -575,8 +591,10 @@ struct Patched {
   double a0, a1, a2, a3, c, b;
 };
 
-template <int MODE>
+template <int MODEP>
 __device__ void walk(const CommitArgs& A, WalkLDS& S) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   constexpr bool STRICT = (MODE == CA_FF || MODE == VBP_BF);
   constexpr bool BEST = (MODE == CA_BF || MODE == VBP_BF);
   const int lane = lane_id();
@@ -717,8 +735,13 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
             const int ck = A.rtb ? grp : anc;
             if (ck != X[r].anc) {
               X[r].anc = ck;
-              X[r].c = S.csum[anc * A.Z + X[r].z];
-              X[r].b = A.rtb ? A.rtb[(size_t)grp * A.H + X[r].id] : S.bsum[anc * A.Z + X[r].z];
+              if constexpr (WIDE) {
+                X[r].c = A.csum[anc * A.Z + X[r].z];
+                X[r].b = A.rtb ? A.rtb[(size_t)grp * A.H + X[r].id] : A.bsum[anc * A.Z + X[r].z];
+              } else {
+                X[r].c = S.csum[anc * A.Z + X[r].z];
+                X[r].b = A.rtb ? A.rtb[(size_t)grp * A.H + X[r].id] : S.bsum[anc * A.Z + X[r].z];
+              }
             }
             k1[r] = ca_score_bits(X[r].c, s2, X[r].b, t1);   // must beat the best so far
           } else {
@@ -881,8 +904,10 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
 #endif
 }
 
-template <int MODE>
+template <int MODEP>
 __global__ __launch_bounds__(WALK_THREADS) void commit_kernel(CommitArgs A) {
+  constexpr int MODE = MODEP & 7;             // (MODEP: the policy, + WALK_WIDE for a wide round)
+  [[maybe_unused]] constexpr bool WIDE = (MODEP & WALK_WIDE) != 0;
   if (A.cmap) {                               // epoch walk: this workgroup's chain
     const int b = blockIdx.x;
     const int base = A.coff[b];
@@ -897,7 +922,7 @@ __global__ __launch_bounds__(WALK_THREADS) void commit_kernel(CommitArgs A) {
   // val starts as "not dead": a loader can see a key the walker is inserting before its value
   // (loaders only act on H_DEAD, which is final, so a stale live value is merely conservative)
   for (int i = tid; i < WH_SLOTS; i += WALK_THREADS) { S.hk[i].key = H_EMPTY; S.hk[i].val = H_PENDING; }
-  if (MODE == CA_BF)
+  if (MODE == CA_BF && !WIDE)
     for (int i = tid; i < A.Z * A.Z; i += WALK_THREADS) { S.csum[i] = A.csum[i]; S.bsum[i] = A.bsum[i]; }
   if (tid < RING) { S.flag[tid] = -1; S.flagB[tid] = -1; }
   if (A.cmap) {                               // the chain's segment starts (chain-local), then nt
@@ -910,8 +935,8 @@ __global__ __launch_bounds__(WALK_THREADS) void commit_kernel(CommitArgs A) {
   if (tid == 0) { S.done = 0; S.stop = 0; S.nl_init = 0; S.nl_pub = 0; S.committed = -1; }
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (wave == 0) walk<MODE>(A, S);
-  else produce<MODE>(A, S, wave - 1);
+  if (wave == 0) walk<MODEP>(A, S);
+  else produce<MODEP>(A, S, wave - 1);
 }
 
 // The walk asks for the whole CU's LDS so no block of a concurrently running score or merge
@@ -931,6 +956,8 @@ hipError_t init_kernel_attrs() {
   if (r != hipSuccess) e = r;
   r = hipFuncSetAttribute((const void*)commit_kernel<VBP_BF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   if (r != hipSuccess) e = r;
+  r = hipFuncSetAttribute((const void*)commit_kernel<CA_BF + WALK_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  if (r != hipSuccess) e = r;
   return e;
 }
 
@@ -939,6 +966,10 @@ void launch_commit(const CommitArgs& a, hipStream_t st) { launch_commit_chains(a
 void launch_commit_chains(const CommitArgs& a, int nchains, hipStream_t st) {
   const size_t lds = WALK_LDS_BYTES;
   const dim3 grid(nchains), block(WALK_THREADS);
+  if (a.mode == CA_BF && a.Z > ZMAX) {
+    PVT_LAUNCH(commit_kernel<CA_BF + WALK_WIDE>, grid, block, lds, st, a);
+    return;
+  }
   switch (a.mode) {
     case CA_FF: PVT_LAUNCH(commit_kernel<CA_FF>, grid, block, lds, st, a); break;
     case CA_BF: PVT_LAUNCH(commit_kernel<CA_BF>, grid, block, lds, st, a); break;

@@ -29,8 +29,17 @@ MODE_NAMES = {PVT_CA_FF: "cost_aware_ff", PVT_CA_BF: "cost_aware_bf", PVT_OPP: "
 PVT_K_SCORE, PVT_K_MERGE, PVT_K_COMMIT, PVT_K_OTHER = range(4)
 
 # Resident rounds / scenario batches (pvt_place_batch).
+PVT_MAX_ZONES = 512          # pvt_round.n_zones bound (include/pivot_place.h)
 PVT_RESIDENT_MAX_HOSTS = 4096
+PVT_RESIDENT_WIDE_MAX_HOSTS = 2048   # cost_aware / mixed batches with more than 32 zones
 PVT_RESIDENT_MAX_TASKS = 4096
+PVT_FAST_ZONES = 32          # up to here a round runs the fast paths (csrc ZMAX)
+
+
+def resident_max_hosts(n_zones):
+    """Hosts of a round a resident batch certainly takes (a batch holding a round of more than
+    PVT_FAST_ZONES zones may run the wide kernels, which take fewer)."""
+    return PVT_RESIDENT_MAX_HOSTS if n_zones <= PVT_FAST_ZONES else PVT_RESIDENT_WIDE_MAX_HOSTS
 
 # Algorithmic bytes per (task, host) candidate, SURVEY.md §8(d).
 BYTES_PER_CANDIDATE = {PVT_CA_FF: 36, PVT_CA_BF: 36, PVT_OPP: 32, PVT_VBP_FF: 32, PVT_VBP_BF: 36}

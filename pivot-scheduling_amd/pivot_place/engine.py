@@ -35,6 +35,7 @@ def load_library(path=None):
     c_int, c_void_p = ctypes.c_int, ctypes.c_void_p
     sig = {
         "pvt_abi_version": ([], c_int),
+        "pvt_max_zones": ([], c_int),
         "pvt_ctx_create": ([c_int, ctypes.POINTER(c_void_p)], c_int),
         "pvt_ctx_destroy": ([c_void_p], c_int),
         "pvt_ctx_set_stream": ([c_void_p, c_void_p], c_int),
@@ -82,9 +83,17 @@ def load_library(path=None):
     if lib.pvt_abi_version() != _abi.PVT_ABI_VERSION:
         raise OSError("pivot_place ABI mismatch: library %d, binding %d"
                       % (lib.pvt_abi_version(), _abi.PVT_ABI_VERSION))
+    if lib.pvt_max_zones() != _abi.PVT_MAX_ZONES:
+        raise OSError("pivot_place zone bound mismatch: library %d, binding %d"
+                      % (lib.pvt_max_zones(), _abi.PVT_MAX_ZONES))
     if path is None:
         _lib = lib
     return lib
+
+
+def max_zones():
+    """The loaded library's bound on ``pvt_round.n_zones`` (pvt_max_zones)."""
+    return int(load_library().pvt_max_zones())
 
 
 def _torch():
@@ -539,7 +548,7 @@ class PlacementEngine:
         if r.n_tasks == 0:
             return True
         max_hosts = min(getattr(self, "_resident_max", _abi.PVT_RESIDENT_MAX_HOSTS),
-                        _abi.PVT_RESIDENT_MAX_HOSTS)   # the C side's resident_fits limit
+                        _abi.resident_max_hosts(r.n_zones))   # the C side's resident_fits limit
         ok = r.n_hosts <= max_hosts and r.n_tasks <= _abi.PVT_RESIDENT_MAX_TASKS
         if ca_args is not None:
             n_storage = len(ca_args[5])

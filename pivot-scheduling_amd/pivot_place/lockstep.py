@@ -190,9 +190,12 @@ class LockstepDriver:
         self.stats["place_calls"] += len(calls)
         eng = self.engine
         batched, rest = [], []
+        # a batch holding a round of more than PVT_FAST_ZONES zones takes fewer hosts per round
+        wide = any(c.args[0].n_zones > _abi.PVT_FAST_ZONES for c in calls)
         for c in calls:
             ca = c.args[1:] if c.kind == "place_ca" else None
-            if hasattr(eng, "place_host_batch") and eng.host_batch_fits(c.args[0], ca):
+            if hasattr(eng, "place_host_batch") and eng.host_batch_fits(c.args[0], ca) and \
+                    not (wide and c.args[0].n_hosts > _abi.PVT_RESIDENT_WIDE_MAX_HOSTS):
                 batched.append(c)
             else:
                 rest.append(c)
@@ -226,7 +229,8 @@ class LockstepDriver:
                     self.stats["place_launches"] += 1
                 c.done = True
                 continue
-            fits = (r.n_tasks > 0 and r.n_hosts <= _abi.PVT_RESIDENT_MAX_HOSTS
+            fits = (r.n_tasks > 0 and r.n_hosts <= (_abi.PVT_RESIDENT_WIDE_MAX_HOSTS if wide else
+                                                    _abi.PVT_RESIDENT_MAX_HOSTS)
                     and r.n_tasks <= _abi.PVT_RESIDENT_MAX_TASKS)
             if fits:
                 by_mode.setdefault(r.mode, []).append(c)

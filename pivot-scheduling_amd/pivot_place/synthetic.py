@@ -4,7 +4,8 @@ The reference cannot build these sizes (it creates O(H^2) route objects, resourc
 so they are defined here from its data:
 
 - zones: the first ``n_zones`` (default 20) zones of locality.yml order, cost table as is,
-  bw x U(.95, 1.05) jitter with seed 0 (pivot_place.locality).
+  bw x U(.95, 1.05) jitter with seed 0 (pivot_place.locality). More than the file's 31 zones:
+  ``wide_zone_tables`` (copies of the 31, a surcharge between copies).
 - hosts: capacity (16, 131072, 100, 1) like sim.py's defaults (alibaba/sim.py:23-32), zone
   i % Z (resources/gen.py:46); availability from RandomState(seed): cpus = 0.5 * randint(0, 33),
   mem = uniform(0, 131072), disk = 100, gpus = 1.
@@ -48,6 +49,29 @@ def mt_state_of(seed):
     return out
 
 
+BASE_ZONES = 31   # zones of locality.yml
+
+
+def wide_zone_tables(n_zones, seed=0):
+    """(cost, bw) for ``n_zones`` zones, more than locality.yml lists (up to PVT_MAX_ZONES).
+
+    Zone i is base zone ``i % 31`` of ``zone_tables(0)`` in copy ``i // 31`` (a further provider
+    with the same regions). cost is the base entry, plus 0.01 * (1 + |copy distance|) between
+    different copies, so the zero-cost pairs (a zone with itself, zones of one region) stay
+    inside a copy and every other sum is positive; bw is the base entry times a fresh
+    U(.95, 1.05) per ordered pair from RandomState(seed), so all rows differ."""
+    Z = int(n_zones)
+    if not 1 <= Z <= _abi.PVT_MAX_ZONES:
+        raise ValueError("n_zones %d outside [1, %d]" % (Z, _abi.PVT_MAX_ZONES))
+    base_cost, base_bw = zone_tables(0)
+    i = np.arange(Z)
+    b, c = i % BASE_ZONES, i // BASE_ZONES
+    dc = np.abs(c[:, None] - c[None, :])
+    cost = base_cost[np.ix_(b, b)] + np.where(dc > 0, 0.01 * (1 + dc), 0.0)
+    bw = base_bw[np.ix_(b, b)] * np.random.RandomState(seed).uniform(.95, 1.05, size=(Z, Z))
+    return np.ascontiguousarray(cost), np.ascontiguousarray(bw)
+
+
 def make_round(mode, n_hosts, n_tasks, seed=20261015, n_zones=20, sort_tasks=None,
                sort_hosts=True):
     """One synthetic round for ``mode`` (a PVT_* constant) as host arrays."""
@@ -66,7 +90,7 @@ def make_round(mode, n_hosts, n_tasks, seed=20261015, n_zones=20, sort_tasks=Non
     dem[1] = mem[rows] * MEM_SCALE_FACTOR
     anchors = rs.randint(0, n_zones, size=T)
     rank = rs.permutation(H).astype(np.uint32)
-    cost, bw = zone_tables(0, n_zones)
+    cost, bw = zone_tables(0, n_zones) if n_zones <= BASE_ZONES else wide_zone_tables(n_zones, 0)
     kw = {}
     if mode in (_abi.PVT_CA_FF, _abi.PVT_CA_BF):
         first = {}
