@@ -158,6 +158,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
   if (const char* e = getenv("PVT_EPOCH_PLAN")) ctx->t_epoch_plan = atoi(e);           // A/B
   if (const char* e = getenv("PVT_ZPRE")) ctx->t_zpre = atoi(e) != 0;                  // A/B
   if (const char* e = getenv("PVT_CHAIN_TAB")) ctx->t_chain_tab = atoi(e) != 0;        // A/B
+  if (const char* e = getenv("PVT_EPOCH_TAIL")) ctx->t_epoch_tail = atoi(e) != 0;      // A/B
   if (const char* e = getenv("PVT_MERGE_SMALL")) ctx->t_merge_bitonic = atoi(e) == 0;  // A/B
   if (const char* e = getenv("PVT_RES_WAVES")) ctx->res_waves = atoi(e) == 8 ? 8 : atoi(e) == 2 ? 2 : atoi(e) == 1 ? 1 : 4;  // A/B
   *out = ctx;
@@ -178,7 +179,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->ksorttmp, &ctx->kflag, &ctx->ep_dev, &ctx->wres, &ctx->hmin, &ctx->cmax, &ctx->fwin,
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
-                 &ctx->zwin, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
+                 &ctx->zwin, &ctx->zundo, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
                  &ctx->chk_owner};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);

@@ -30,14 +30,15 @@ using namespace pvt;
 static constexpr int EPOCH_SEGS = 64;
 static constexpr int EPOCH_MAX = 16384;
 // ep_dev / ep_host words: uploaded [seg_off | seg_chain | seg_cstart | coff | csoff | cseg |
-// cmap], then read back [status (2 per chain) | bad (per segment)]
+// cmap], then read back [status (2 per chain) | bad (per segment) | res | safe (per segment) |
+// cert (per chain: the frontier walk's certificate word, written to ep_host only)]
 static constexpr int EP_SEG_OFF = 0, EP_SEG_CHAIN = EP_SEG_OFF + EPOCH_SEGS + 1,
                      EP_SEG_CSTART = EP_SEG_CHAIN + EPOCH_SEGS, EP_COFF = EP_SEG_CSTART + EPOCH_SEGS,
                      EP_CSOFF = EP_COFF + EPOCH_SEGS + 1, EP_CSEG = EP_CSOFF + EPOCH_SEGS + 1,
                      EP_CMAP = EP_CSEG + EPOCH_SEGS, EP_STATUS = EP_CMAP + EPOCH_MAX,
                      EP_BAD = EP_STATUS + 2 * EPOCH_SEGS, EP_RES = EP_BAD + EPOCH_SEGS,
-                     EP_SAFE = EP_RES + 8;
-static constexpr int EP_WORDS = EP_SAFE + EPOCH_SEGS;
+                     EP_SAFE = EP_RES + 8, EP_CERT = EP_SAFE + EPOCH_SEGS;
+static constexpr int EP_WORDS = EP_CERT + EPOCH_SEGS;
 static constexpr int KEYED_FRONTIER_MIN = 32;   // group tasks worth a frontier-walk launch
 static constexpr int ORDERED_FRONTIER_MIN = 32;  // tasks a frontier attempt must place to go on
 static constexpr int ORDERED_FRONTIER_TASKS = 4096;   // tasks per frontier attempt (default;
@@ -101,6 +102,7 @@ struct RoundState {
   int if_t0 = 0, if_nt = 0, if_lb = 0, pt0 = 0, plb = 0;   //   inherited touched hosts
   std::vector<int> egs, ega;      // cost_aware best-fit epochs: group starts (+ T) and anchors
   std::vector<int> ecomp;         // zone -> its component of zones joined by zero egress cost
+  std::vector<int> ezcomp;        //   the same whatever PVT_EPOCH_PLAN says (the epoch tail's condition 2)
   bool in_epoch = false;          // lists scored for an epoch (place_epochs)
   bool ofront = false;            // ordered first-fit rounds walked by the frontier walk
   int ofh = 0;                    // hosts the frontier window is taken from
@@ -188,6 +190,7 @@ struct pvt_ctx {
   int t_epoch_plan = 1;           // PVT_EPOCH_PLAN: 0 = epoch chains by distinct zone only
   int t_zpre = 1;                 // PVT_ZPRE: 0 = every frontier walk builds its own window
   int t_chain_tab = 1;            // PVT_CHAIN_TAB: 0 = chain tables uploaded before the walk
+  int t_epoch_tail = 1;           // PVT_EPOCH_TAIL: 0 = every frontier-walked epoch runs the tail kernels
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
   int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
   int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
@@ -200,6 +203,7 @@ struct pvt_ctx {
   Buf hmin;                       // frontier walk: per-dimension host minima (partials)
   Buf cmax;                       // frontier-walked epochs: chains' largest demands
   Buf zwin;                       // the first epoch's zero-cost windows (ZoneWindows)
+  Buf zundo;                      // frontier walks' optimistic apply: per chain, what undoes it (ZwUndo)
   int32_t* ep_host = nullptr;     // pinned staging of ep_dev
   int32_t* ep_hdev = nullptr;     // ep_host's device address (the accept kernel's readback)
   pvt_round* rstage = nullptr;    // pvt_place_batch: descriptors staged for the device (pinned)
@@ -336,6 +340,7 @@ int zero_cost_components(pvt_ctx* ctx);
 int epoch_groups(pvt_ctx* ctx);
 void epoch_plan(const RoundState& R, int t0, EpochPlan& P, bool whole = false);
 int upload_chain_tables(pvt_ctx* ctx, const EpochPlan& E);
+void epoch_tail(pvt_ctx* ctx, const EpochArgs& ea, bool validate, int accept_nch);
 int ff_epoch(pvt_ctx* ctx, int* adv_out);
 int epoch_frontier_verdict(pvt_ctx* ctx, const EpochPlan& E, int t0, int* need_out, int* adv_out);
 int place_epochs(pvt_ctx* ctx);

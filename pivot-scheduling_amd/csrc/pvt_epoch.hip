@@ -401,13 +401,35 @@ __global__ __launch_bounds__(1024) void epoch_accept_apply_kernel(EpochArgs A, i
   }
 }
 
+// A frontier walk's optimistic apply, taken back (the epoch was not accepted whole): block c, for
+// a chain c that wrote its window back, stores the window's epoch-start rows again (ZwUndo: saved
+// by the walk's prologue; different chains' windows hold disjoint hosts).
+__global__ __launch_bounds__(256) void epoch_undo_kernel(const ZwUndo* undo, uint64_t chains,
+                                                         double* avail, int H) {
+  const int c = blockIdx.x;
+  if (!((chains >> c) & 1ull)) return;
+  const ZwUndo& u = undo[c];
+  const int n = min(max(u.count, 0), ZW_MBIG);
+  for (int p = threadIdx.x; p < n; p += blockDim.x) {
+    const int h = u.id[p];
+    if (h < 0 || h >= H) continue;
+#pragma unroll
+    for (int r = 0; r < 4; r++) avail[(size_t)r * H + h] = u.a[r][p];
+  }
+}
+
+void launch_epoch_undo(const ZwUndo* undo, uint64_t chains, int nchains, double* avail, int H,
+                       hipStream_t st) {
+  if (!chains || nchains <= 0) return;
+  PVT_LAUNCH(epoch_undo_kernel, dim3(nchains), dim3(256), 0, st, undo, chains, avail, H);
+}
+
 void launch_epoch_accept_apply(const EpochArgs& a, int32_t* res, int nchains, hipStream_t st,
                                int32_t* hout, int nwords) {
   PVT_LAUNCH(epoch_accept_apply_kernel, dim3(nchains), dim3(1024), 0, st, a, res, hout, nwords);
 }
 
 void launch_epoch_validate(const EpochArgs& a, hipStream_t st) {
-  PVT_LAUNCH(epoch_final_kernel, dim3(a.nseg), dim3(1024), 0, st, a);
   const int tiles = (CHAIN_MAX + 255) / 256;   // a segment never exceeds its chain's cap
   PVT_LAUNCH(epoch_validate_kernel, dim3(tiles, a.nseg, VAL_SPLIT), dim3(256), 0, st, a);
 }

@@ -236,8 +236,9 @@ struct EpochArgs {
   int nch;
   int32_t* safe;          // [nseg]
 };
+// pair validation (after launch_epoch_final, which zeroes the verdicts it sets)
 void launch_epoch_validate(const EpochArgs& a, hipStream_t st);
-// finality only (no pair validation: first-fit zero-key epochs)
+// finality (alone: first-fit zero-key epochs need no pair validation)
 void launch_epoch_final(const EpochArgs& a, hipStream_t st);
 // apply: the accepted segments [0, n_accept) of each chain, chain by chain in segment order
 void launch_epoch_apply(const EpochArgs& a, int n_accept, int nchains, hipStream_t st);
@@ -245,6 +246,10 @@ void launch_epoch_apply(const EpochArgs& a, int n_accept, int nchains, hipStream
 // (hout: mapped pinned memory) the nwords readback words from a.status copied there
 void launch_epoch_accept_apply(const EpochArgs& a, int32_t* res, int nchains, hipStream_t st,
                                int32_t* hout = nullptr, int nwords = 0);
+// a missed optimistic apply of the frontier walk (ZwalkArgs.undo): the chains of `chains` (bit c:
+// chain c wrote its window back) get their windows' epoch-start rows again
+void launch_epoch_undo(const struct ZwUndo* undo, uint64_t chains, int nchains, double* avail, int H,
+                       hipStream_t st);
 void launch_commit_chains(const CommitArgs& a, int nchains, hipStream_t st);
 // vbp best-fit windows: the one-wave list walk with list cursors (pvt_lwalk.hip); CommitArgs as
 // for launch_commit (no epochs, no stamps). status[0] < nt: refill there (0: the list walk decides)
@@ -310,6 +315,15 @@ struct ZwalkArgs {
   // chain mode, the round's first epoch: windows the grouped order's launch built from the
   // snapshot (a chain uses the one whose zone set covers its anchors' zero-cost zones), or NULL
   const struct ZoneWindows* zpre;
+  // chain mode, optimistic apply (the driver's epoch tail), or NULL: a chain that
+  // walked all its tasks writes its window's capacities to wb (the round's avail) itself; every
+  // chain first saves its window's hosts and start capacities in undo[b], and reports status[0],
+  // status[1] also to hstat[2b], hstat[2b + 1] and its certificate word to hcert[b] (both mapped
+  // pinned): bits 0-3 the dimensions no task of the chain demands (every d[r] is +-0), bits 4-7
+  // the dimensions whose host minimum is at least 2^-287 (best-fit; first-fit reports 0)
+  struct ZwUndo* undo;
+  int32_t* hstat;
+  int32_t* hcert;
   ChainTab tab;           // chain mode: the epoch's chain tables by value (tab.nch > 0), or none
 };
 constexpr int ZW_MIN_PARTS = 256;
@@ -324,6 +338,13 @@ void launch_zwalk_big(const ZwalkArgs& a, int nchains, hipStream_t st);
 void launch_zwalk_ff(const ZwalkArgs& a, int nchains, hipStream_t st);
 void launch_host_absmax(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);
 constexpr int ZW_M = 1024;                 // frontier-walk window hosts
+constexpr int ZW_MBIG = 3072;              // the large window (a retry for chains that outgrow ZW_M)
+// What undoes a chain's optimistic apply: its window's hosts and their epoch-start capacities.
+struct ZwUndo {
+  int32_t count, pad[3];
+  int32_t id[ZW_MBIG];
+  double a[4][ZW_MBIG];
+};
 void launch_zwalk_keyed(const ZwalkArgs& a, bool strict, hipStream_t st);
 // ordered first-fit frontier: flags[h - lo] = host h in [lo, hs) fits the smallest demand of
 // tasks dem[0, n)

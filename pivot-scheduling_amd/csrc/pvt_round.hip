@@ -1133,7 +1133,7 @@ int pvt::place_windowed(pvt_ctx* ctx, const pvt_round* r) {
   ctx->n_epochs = ctx->n_segs = ctx->n_rejected = 0;
   ctx->n_zchains = ctx->n_gchains = ctx->n_longest = 0;
   if ((rc = epoch_groups(ctx))) return rc;
-  rc = ctx->rs.egs.empty() ? place_pipelined(ctx) : place_epochs(ctx);
+  rc = (ctx->rs.egs.empty() || ctx->rs.ffe) ? place_pipelined(ctx) : place_epochs(ctx);
   ctx->rs.active = false;
   if (rc) {
     (void)hipStreamSynchronize(ctx->side);

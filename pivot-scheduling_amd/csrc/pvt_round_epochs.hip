@@ -26,6 +26,15 @@ int pvt::zero_cost_components(pvt_ctx* ctx) {
     for (int z = 0; z < Z; z++)
       if (cost[(size_t)a * Z + z] + cost[(size_t)z * Z + a] == 0.0) R.ecomp[root(a)] = root(z);
   for (int z = 0; z < Z; z++) R.ecomp[z] = root(z);
+  // the components proper, whatever the plan (under PVT_EPOCH_PLAN=0 chains of one component share
+  // window hosts: the epoch tail's condition 2)
+  R.ezcomp.resize(Z);
+  for (int z = 0; z < Z; z++) R.ezcomp[z] = z;
+  auto zroot = [&](int z) { while (R.ezcomp[z] != z) z = R.ezcomp[z] = R.ezcomp[R.ezcomp[z]]; return z; };
+  for (int a = 0; a < Z; a++)
+    for (int z = 0; z < Z; z++)
+      if (cost[(size_t)a * Z + z] + cost[(size_t)z * Z + a] == 0.0) R.ezcomp[zroot(a)] = zroot(z);
+  for (int z = 0; z < Z; z++) R.ezcomp[z] = zroot(z);
   return PVT_OK;
 }
 
@@ -34,6 +43,7 @@ int pvt::zero_cost_components(pvt_ctx* ctx) {
 int pvt::epoch_groups(pvt_ctx* ctx) {
   RoundState& R = ctx->rs;
   const pvt_round* r = &R.r;
+  if (R.ffe) return PVT_OK;                   // keyed rounds: ff_epoch plans on round_begin's groups
   R.egs.clear();
   R.ega.clear();
   const int T = R.T;
@@ -159,6 +169,98 @@ static bool chain_tab(pvt_ctx* ctx, const EpochPlan& E, ChainTab& t) {
   return true;
 }
 
+// ---------------------------------------------------------------- the epoch tail
+// A frontier-walked epoch whose chains all walk to their end needs none of the kernels after the
+// walk: each chain writes its window back itself (ZwalkArgs.undo: the optimistic
+// apply) and the host reads the verdict from the chains' own words. Where the walk owns its
+// window: unsharded rounds of at most ZMAX zones without realtime bandwidth.
+static bool tail_eligible(pvt_ctx* ctx) {
+  const RoundState& R = ctx->rs;
+  return ctx->t_epoch_tail && !R.sharded && R.world <= 1 && !R.r.rt_bw && R.Z <= ZMAX;
+}
+
+// Condition 2: no two chains hold anchors of one zero-cost component. A chain's zones U (its
+// anchors' zero-cost zones) and a prebuilt window's zones (ZoneWindows: zones of one component)
+// lie inside its anchors' components, so the chains' windows are then disjoint: a chain's
+// write-back touches no host another chain reads or commits to. False under PVT_EPOCH_PLAN=0
+// whenever two chains' U intersect.
+static bool tail_chains_apart(const RoundState& R, int t0, const EpochPlan& E) {
+  if ((int)R.ezcomp.size() != R.Z || R.Z > ZMAX) return false;
+  size_t g = 0;
+  while (g + 1 < R.egs.size() && R.egs[g + 1] <= t0) g++;
+  const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
+  if (nch > 64) return false;
+  std::vector<uint32_t> comps(nch, 0u);
+  for (int k = 0; k < nseg; k++, g++) {      // (segment k is the epoch's k-th group, epoch_plan)
+    if (g >= R.ega.size()) return false;
+    const int z = R.ega[g];
+    if (z >= 0 && z < R.Z) comps[E.chain[k]] |= 1u << R.ezcomp[z];   // (else: the walk bails)
+  }
+  uint32_t seen = 0;
+  for (int c = 0; c < nch; c++) {
+    if (seen & comps[c]) return false;
+    seen |= comps[c];
+  }
+  return true;
+}
+
+// The optimistic apply's arguments of the frontier walk.
+static int tail_walk_args(pvt_ctx* ctx, ZwalkArgs& za) {
+  ENSURE(ctx->zundo, sizeof(ZwUndo) * (size_t)EPOCH_SEGS);
+  za.undo = P<ZwUndo>(ctx->zundo);
+  za.wb = ctx->rs.r.avail;
+  za.hstat = ctx->ep_hdev + EP_STATUS;
+  za.hcert = ctx->ep_hdev + EP_CERT;
+  return PVT_OK;
+}
+
+// After the walk's synchronisation: the epoch is accepted whole iff (1) every chain walked all its
+// tasks with no certificate failed, and (3, best-fit) some dimension no chain demands has a host
+// minimum of at least 2^-287 -- then every log entry keeps its start value there, which exceeds
+// the epoch's largest demand (+-0) by 2^-287: every segment is safe, as epoch_final_kernel would
+// find, and epoch_accept_apply_kernel would accept all of them and write each host's last entry,
+// the window state the chains wrote themselves. (Condition 2 was decided before the launch.)
+// *wrote: the chains that wrote their windows back.
+static bool tail_accepted(pvt_ctx* ctx, const EpochPlan& E, bool best_fit, uint64_t* wrote) {
+  const int32_t* host = ctx->ep_host;
+  const int nch = (int)E.segs.size();
+  uint64_t w = 0;
+  int cert = 0xff;
+  for (int c = 0; c < nch; c++) {
+    if (host[EP_STATUS + 2 * c] == E.len[c] && host[EP_STATUS + 2 * c + 1] == 0) w |= 1ull << c;
+    cert &= host[EP_CERT + c];
+  }
+  *wrote = w;
+  const bool all = w == (nch >= 64 ? ~0ull : (1ull << nch) - 1ull);
+  return all && (!best_fit || ((cert & 0xf) & (cert >> 4)) != 0);
+}
+
+// A missed optimistic apply: the chains that wrote back get their start rows again, before the
+// tail kernels run on the epoch's start state as ever.
+static void tail_undo(pvt_ctx* ctx, uint64_t wrote, int nch) {
+  Scope sc(ctx, PVT_K_OTHER, 0, 0, nullptr, "epoch_undo_kernel");
+  launch_epoch_undo(P<ZwUndo>(ctx->zundo), wrote, nch, ctx->rs.r.avail, ctx->rs.H, ctx->stream);
+}
+
+// The tail kernels, each in a scope of its own name: finality, pair validation (validate), and
+// (accept_nch > 0) the accepted prefix with its apply and the mapped readback.
+void pvt::epoch_tail(pvt_ctx* ctx, const EpochArgs& ea, bool validate, int accept_nch) {
+  hipStream_t st = ctx->stream;
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, 0, nullptr, "epoch_final_kernel");
+    launch_epoch_final(ea, st);
+  }
+  if (validate) {
+    Scope sc(ctx, PVT_K_OTHER, 0, 0, nullptr, "epoch_validate_kernel");
+    launch_epoch_validate(ea, st);
+  }
+  if (accept_nch > 0) {
+    Scope sc(ctx, PVT_K_OTHER, 0, 0, nullptr, "epoch_accept_apply_kernel");
+    launch_epoch_accept_apply(ea, P<int32_t>(ctx->ep_dev) + EP_RES, accept_nch, st,
+                              ctx->ep_hdev + EP_STATUS, EP_WORDS - EP_STATUS);   // (readback: mapped)
+  }
+}
+
 // cost_aware first-fit with sort_hosts (cost_aware.py:99-127): an epoch of WHOLE groups from
 // the group start R.t0, chains of zero-cost components walked side by side by the first-fit
 // zero-key chain walk (pvt_zwalk.hip, FF). Every task it proves takes the lowest-index strictly
@@ -181,7 +283,6 @@ int pvt::ff_epoch(pvt_ctx* ctx, int* adv_out) {
   ENSURE(ctx->ep_dev, sizeof(int32_t) * EP_WORDS);
   ENSURE(ctx->wres, sizeof(WinRec) * (size_t)EPOCH_MAX);
   ENSURE(ctx->hmin, sizeof(double) * 4 * ZW_MIN_PARTS);
-  int32_t* dev = P<int32_t>(ctx->ep_dev);
   int32_t* host = ctx->ep_host;
   int rc;
   {
@@ -190,22 +291,36 @@ int pvt::ff_epoch(pvt_ctx* ctx, int* adv_out) {
   }
   ZwalkArgs za = zwalk_chain_args(ctx, t0);
   if (!(ctx->t_chain_tab && chain_tab(ctx, E, za.tab)) && (rc = upload_chain_tables(ctx, E))) return rc;
+  // the epoch tail: chains of different components write their windows back themselves, and an
+  // epoch all of whose chains completed needs no launch after the walk (no pair validation here)
+  // (chains that share a component, PVT_EPOCH_PLAN=0, would take the same hosts side by side and
+  // nothing here checks pairs: those groups go to the keyed path)
+  if (!tail_chains_apart(R, t0, E)) return PVT_OK;
+  const bool opt = tail_eligible(ctx);
+  if (opt && (rc = tail_walk_args(ctx, za))) return rc;
   {
     Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
     launch_zwalk_ff(za, nch, st);
   }
-  EpochArgs ea = epoch_args(ctx, t0, nt, nseg);
-  ea.whole = 1;
-  {
-    Scope sc(ctx, PVT_K_OTHER, 0, 0);
-    launch_epoch_final(ea, st);
-    launch_epoch_accept_apply(ea, dev + EP_RES, nch, st, ctx->ep_hdev + EP_STATUS,
-                              EP_WORDS - EP_STATUS);   // (readback: mapped)
-  }
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipStreamSynchronize(st));
   ctx->n_epochs++;
   ctx->n_segs += nseg;
+  if (opt) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(st));
+    uint64_t wrote = 0;
+    if (tail_accepted(ctx, E, false, &wrote)) {
+      ctx->n_zchains += nch;
+      ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
+      *adv_out = nt;
+      return PVT_OK;
+    }
+    tail_undo(ctx, wrote, nch);
+  }
+  EpochArgs ea = epoch_args(ctx, t0, nt, nseg);
+  ea.whole = 1;
+  epoch_tail(ctx, ea, false, nch);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(st));
   int proven = 0;
   for (int c = 0; c < nch; c++) proven += host[EP_STATUS + 2 * c] == E.len[c];
   ctx->n_zchains += proven;
@@ -293,10 +408,7 @@ int pvt::place_epochs(pvt_ctx* ctx) {
     EpochArgs ea = epoch_args(ctx, t0, nt, nseg);
     ea.rtb = r->rt_bw;
     auto validate_and_read = [&]() -> int {
-      {
-        Scope sc(ctx, PVT_K_OTHER, 0, 0);
-        launch_epoch_validate(ea, st);
-      }
+      epoch_tail(ctx, ea, true, 0);
       HIPCHK(hipGetLastError());
       HIPCHK(hipMemcpyAsync(host + EP_STATUS, dev + EP_STATUS, sizeof(int32_t) * (EP_WORDS - EP_STATUS),
                             hipMemcpyDeviceToHost, st));
@@ -315,6 +427,13 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       ea.coff = dev + EP_COFF;
       ea.nch = nch;
       ea.safe = dev + EP_SAFE;
+      // the epoch tail: chains of different components write their windows back themselves
+      // (chains that share a component, PVT_EPOCH_PLAN=0, can win each other's hosts at score 0:
+      // no write-back, and no fast path in the validation -- every pair is checked)
+      const bool apart = tail_chains_apart(R, t0, E);
+      const bool opt = apart && tail_eligible(ctx);
+      if (!apart) ea.cmax = nullptr;
+      if (opt && (rc = tail_walk_args(ctx, za))) return rc;
       {
         Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
         if (big) launch_zwalk_big(za, nch, st);
@@ -323,16 +442,24 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       const bool was_big = big;
       big = false;
       HIPCHK(hipGetLastError());
+      if (opt) {
+        // one synchronisation, the verdict from the chains' own words: accepted whole, no further
+        // launch; else the write-backs are undone and the tail decides as ever
+        HIPCHK(hipStreamSynchronize(st));
+        uint64_t wrote = 0;
+        if (tail_accepted(ctx, E, true, &wrote)) {
+          ctx->n_zchains += nch;
+          ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
+          t0 += nt;
+          continue;
+        }
+        tail_undo(ctx, wrote, nch);
+      }
       // validation, the accepted prefix and its apply all on the device, then one readback. A
       // chain the frontier walk could not prove is not accepted past its first segment; the
       // next epoch then walks its chains with candidate lists (force_lists) -- or, when a chain
       // only ran out of window hosts, once more with the large window.
-      {
-        Scope sc(ctx, PVT_K_OTHER, 0, 0);
-        launch_epoch_validate(ea, st);
-        launch_epoch_accept_apply(ea, dev + EP_RES, nch, st, ctx->ep_hdev + EP_STATUS,
-                                  EP_WORDS - EP_STATUS);   // (readback: mapped)
-      }
+      epoch_tail(ctx, ea, true, nch);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(st));
       int adv = 0;

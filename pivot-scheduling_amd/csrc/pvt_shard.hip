@@ -320,12 +320,7 @@ static int shard_frontier_commit(pvt_ctx* ctx, const void* packages) {
     ea.coff = dev + EP_COFF;
     ea.nch = nch;
     ea.safe = dev + EP_SAFE;
-    {
-      Scope sc(ctx, PVT_K_OTHER, 0, 0);
-      launch_epoch_validate(ea, st);
-      launch_epoch_accept_apply(ea, dev + EP_RES, nch, st, ctx->ep_hdev + EP_STATUS,
-                                EP_WORDS - EP_STATUS);   // (readback: mapped)
-    }
+    epoch_tail(ctx, ea, true, nch);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(st));
     int need = 0, adv = 0;

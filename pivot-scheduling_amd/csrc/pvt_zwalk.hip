@@ -30,6 +30,12 @@
 // a key of 0 only when the score's bits are 0). The log and the chain's progress have the
 // format of the list walk's chain mode, so validation, finality and apply are unchanged.
 //
+// Optimistic apply (ZwalkArgs.undo, the driver's epoch tail): a chain that walked all its tasks
+// holds each of its hosts' final state in its window and writes it to global availability
+// itself; with every chain's report in the host's mapped words, an epoch whose chains all
+// completed needs no kernel after this one. The prologue saves the window's start rows (ZwUndo)
+// for the epochs the host does not accept whole.
+//
 // FF: the same chain walk for cost_aware FIRST-fit with sort_hosts (scheduler/cost_aware.py:
 // 99-127). A group's hosts are taken in the order of the frozen key c*df/(||avail||*bw); hosts
 // of the anchor's zero-cost zones have key exactly 0 and lead that order in index order, so
@@ -51,7 +57,6 @@
 
 namespace pvt {
 
-constexpr int ZW_MBIG = 3072;              // the large window (a retry for chains that outgrow ZW_M)
 constexpr int ZW_THREADS = 256;
 constexpr int ZW_WAVES = ZW_THREADS / 64;
 constexpr int ZW_SCAN = 8;                 // 16-byte zone loads (4 hosts) per thread per window-build pass
@@ -88,6 +93,7 @@ struct ZwalkLDS {
   uint32_t amask[ZMAX];                    // anchor -> its zero-cost zones
   uint32_t umask;
   int32_t nwin, bail;
+  int32_t touch[WM / 64];                  // optimistic apply: chunks committed to in LDS (past p0 / pb)
 };
 
 // Wave reductions of doubles, uniform results: DPP row prefix steps (lane 15 of each 16-lane row
@@ -257,6 +263,12 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   const bool segm = !KEYED && (tabm || A.cseg);   // group segment starts break runs
   int32_t* status = A.status + 2 * b;
   const int Z = A.Z, H = A.H;
+  // the chain's report (one thread): the device words the epoch kernels read and, with the
+  // optimistic apply, the host's mapped words -- no later kernel copies them
+  auto report = [&](int s0, int s1) {
+    status[0] = s0; status[1] = s1;
+    if (!KEYED && A.hstat) { A.hstat[2 * b] = s0; A.hstat[2 * b + 1] = s1; }
+  };
 
   // Every load the prologue needs that depends on nothing else is issued first (the zone
   // tables, the host minima, the chain's first task positions, its segment range), so the
@@ -330,6 +342,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   }
   if (tid == 0) { S.umask = 0; S.nwin = 0; S.bail = 0; }
   if (tid < CHAIN_MAX / 64) S.sbits[tid] = 0;
+  if (tid < WM / 64) S.touch[tid] = 0;
   __syncthreads();
   if (!KEYED && tid < Z) {                   // anchor row -> zero-cost zone mask
     uint32_t m = 0;
@@ -435,6 +448,15 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     ha[r] = FF ? nan_max(ha[r], S.red[0][8 + r]) : fmin(ha[r], S.red[0][8 + r]);
   }
   if (!KEYED && A.cmax && tid < 4) A.cmax[b * 4 + tid] = mx[tid];   // (the validation's fast path)
+  if (!KEYED && A.hcert && tid == 0) {       // the certificate word of the host's verdict
+    int cert = 0;
+    if (!FF) {
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        cert |= ((mx[r] <= 0.0 && mn[r] >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
+    }
+    A.hcert[b] = cert;
+  }
   bool sep = KEYED;
   if (FF) {                                  // certificates (2') and (3'): bounded capacities,
     sep = true;                              // demands >= 0
@@ -446,7 +468,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   }
   uint32_t U = S.umask;
   if (S.bail || !sep || nt <= 0 || (!KEYED && nt > CHAIN_MAX)) {
-    if (tid == 0) { status[0] = 0; status[1] = (KEYED || nt <= 0) ? 0 : 1; }
+    if (tid == 0) report(0, (KEYED || nt <= 0) ? 0 : 1);
     return;
   }
   const FrontierSlot* pw = A.pwin ? A.pwin + (KEYED ? 0 : b) : nullptr;
@@ -489,6 +511,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   const uint64_t t_win = zstamp();
 #endif
   bool wbad = false;
+  // optimistic apply: the window's hosts and start capacities, saved for an undo (plain stores
+  // nothing waits for)
+  ZwUndo* const ud = (!KEYED && A.undo) ? A.undo + b : nullptr;
+  if (ud && tid == 0) ud->count = nwin;
+  static_assert(WM <= ZW_MBIG, "ZwUndo holds every window");
   static_assert(WM % (4 * ZW_THREADS) == 0, "window capacities: four hosts per thread per pass");
   for (int p0 = 0; p0 < WM && p0 < nwin; p0 += 4 * ZW_THREADS) {
     double v[4][4];                          // every gather of the pass in flight at once
@@ -509,6 +536,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           wbad |= !(__builtin_fabs(v[u][r]) <= ZW_BIG);
           S.wa[r][p] = v[u][r];
         }
+        if (ud) {
+          ud->id[p] = S.wid[p];
+#pragma unroll
+          for (int r = 0; r < 4; r++) ud->a[r][p] = v[u][r];
+        }
       }
     }
   }
@@ -518,7 +550,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   const uint64_t t_cap = zstamp();
 #endif
   if (S.bail || nwin == 0) {
-    if (tid == 0) { status[0] = 0; status[1] = KEYED ? 0 : 1; }
+    if (tid == 0) report(0, KEYED ? 0 : 1);
     return;
   }
   // suffix minima of the chain's demands per 64-task batch: a chunk no host of which fits the
@@ -912,6 +944,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           ZW_SEARCH_DONE();
           const int got = run_bulk(IntC<0>{}, x0, x1, x2, x3, xid, d0, d1, d2, d3, fm, R, k);
           if (p < nwin) { S.wa[0][p] = x0; S.wa[1][p] = x1; S.wa[2][p] = x2; S.wa[3][p] = x3; }
+          if (!KEYED && lane == 0) S.touch[c] = 1;
           return got;
         }
       }
@@ -1136,6 +1169,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
                   S.wa[0][q] = c0; S.wa[1][q] = c1; S.wa[2][q] = c2; S.wa[3][q] = c3;
                   S.lg[k][0] = c0; S.lg[k][1] = c1; S.lg[k][2] = c2; S.lg[k][3] = c3;
                   S.lgid[k] = id;
+                  if (!KEYED) S.touch[c] = 1;
                 }
                 found = true;
                 break;
@@ -1180,9 +1214,28 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       for (int r = 0; r < 4; r++) A.wb[(size_t)r * H + h] = S.wa[r][p];
     }
   }
+  if (!KEYED && A.undo && !failed && done == nt) {
+    // optimistic apply: the chain walked all its tasks, so its window holds each host's state after
+    // the chain's last commit to it -- what the epoch's apply would rebuild from the log. The
+    // chunks the walk committed to (the register chunks' range, and those marked in LDS) go to
+    // global availability; the driver undoes it (ZwUndo) if the epoch is not accepted whole.
+    store_chunk(p0);
+    store_b();
+    wave_lds_sync();
+    const int top = max(p0, pb);
+    for (int c = 0; c < nch; c++) {
+      if (c > top && !S.touch[c]) continue;
+      const int p = c * 64 + lane;
+      if (p < nwin) {
+        const int h = S.wid[p];
+#pragma unroll
+        for (int r = 0; r < 4; r++) A.wb[(size_t)r * H + h] = S.wa[r][p];
+      }
+    }
+  }
   // status[0]: tasks proven (their log entries are exact; validation accepts them), status[1]:
   // 1 when a certificate failed there (the rest of the chain is left to the list walk)
-  if (lane == 0) { status[0] = done; status[1] = (failed && !KEYED) ? (exhausted ? 2 : 1) : 0; }
+  if (lane == 0) report(done, (failed && !KEYED) ? (exhausted ? 2 : 1) : 0);
 #ifdef PVT_STAMPS
   if (lane == 0 && A.stamps) {
     const uint64_t t_end = zstamp();
