@@ -217,6 +217,12 @@ int  pvt_epoch_stats(pvt_ctx* ctx, int64_t* epochs, int64_t* segments, int64_t* 
 int  pvt_set_zero_walk(pvt_ctx* ctx, int on);
 int  pvt_zero_walk_stats(pvt_ctx* ctx, int64_t* frontier_chains, int64_t* list_chains,
                          int64_t* longest_chain);
+/*
+ * Frontier chains of the last pvt_place that took the walk's fast prologue (group certificates
+ * from the order launch instead of a pass over the chain's demand rows; PVT_CHAIN_CERT=0 at
+ * context creation turns it off; results identical either way).
+ */
+int  pvt_prologue_stats(pvt_ctx* ctx, int64_t* fast_chains);
 /* Counters of the last pvt_place call: windows run and refills forced by exhausted lists. */
 int  pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills);
 /*

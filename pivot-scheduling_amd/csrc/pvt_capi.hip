@@ -159,6 +159,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
   if (const char* e = getenv("PVT_ZPRE")) ctx->t_zpre = atoi(e) != 0;                  // A/B
   if (const char* e = getenv("PVT_CHAIN_TAB")) ctx->t_chain_tab = atoi(e) != 0;        // A/B
   if (const char* e = getenv("PVT_EPOCH_TAIL")) ctx->t_epoch_tail = atoi(e) != 0;      // A/B
+  if (const char* e = getenv("PVT_CHAIN_CERT")) ctx->t_chain_cert = atoi(e) != 0;      // A/B
   if (const char* e = getenv("PVT_MERGE_SMALL")) ctx->t_merge_bitonic = atoi(e) == 0;  // A/B
   if (const char* e = getenv("PVT_RES_WAVES")) ctx->res_waves = atoi(e) == 8 ? 8 : atoi(e) == 2 ? 2 : atoi(e) == 1 ? 1 : 4;  // A/B
   *out = ctx;
@@ -179,7 +180,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->ksorttmp, &ctx->kflag, &ctx->ep_dev, &ctx->wres, &ctx->hmin, &ctx->cmax, &ctx->fwin,
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
-                 &ctx->zwin, &ctx->zundo, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
+                 &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
                  &ctx->chk_owner};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
@@ -299,6 +300,11 @@ extern "C" int pvt_zero_walk_stats(pvt_ctx* ctx, int64_t* frontier_chains, int64
   if (frontier_chains) *frontier_chains = ctx->n_zchains;
   if (list_chains) *list_chains = ctx->n_gchains;
   if (longest_chain) *longest_chain = ctx->n_longest;
+  return PVT_OK;
+}
+extern "C" int pvt_prologue_stats(pvt_ctx* ctx, int64_t* fast_chains) {
+  if (!ctx) return PVT_EINVAL;
+  if (fast_chains) *fast_chains = ctx->n_fastpro;
   return PVT_OK;
 }
 extern "C" int pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills) {

@@ -149,4 +149,30 @@ __device__ __forceinline__ int wave_incl_scan_dpp(int v) {
   return v + (row > 0 ? r0 : 0) + (row > 1 ? r1 : 0) + (row > 2 ? r2 : 0);
 }
 
+// Wave reductions of doubles, uniform results: DPP row prefix steps (lane 15 of each 16-lane row
+// then holds the row's result), then the four rows by readlane -- no LDS permutes.
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+  const uint64_t b = (uint64_t)__double_as_longlong(v);
+  const uint32_t lo = dpp_u32<CTRL>((uint32_t)b, (uint32_t)b);
+  const uint32_t hi = dpp_u32<CTRL>((uint32_t)(b >> 32), (uint32_t)(b >> 32));
+  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+template <class Op>
+__device__ __forceinline__ double wave_reduce_d(double v, Op op) {
+  v = op(v, dpp_d<DPP_ROW_SHR1>(v));
+  v = op(v, dpp_d<DPP_ROW_SHR2>(v));
+  v = op(v, dpp_d<DPP_ROW_SHR4>(v));
+  v = op(v, dpp_d<DPP_ROW_SHR8>(v));
+  const double r0 = readlane_d(v, 15), r1 = readlane_d(v, 31);
+  const double r2 = readlane_d(v, 47), r3 = readlane_d(v, 63);
+  return op(op(r0, r1), op(r2, r3));
+}
+__device__ __forceinline__ double wave_max_d(double v) {
+  return wave_reduce_d(v, [](double a, double b) { return fmax(a, b); });
+}
+__device__ __forceinline__ double wave_min_d(double v) {
+  return wave_reduce_d(v, [](double a, double b) { return fmin(a, b); });
+}
+
 }  // namespace pvt

@@ -127,6 +127,7 @@ struct RoundState {
   bool ffe = false;               // keyed rounds: first-fit zero-key epochs (ff_epoch)
   bool hmin_pre = false;          // the first epoch's host minima were queued by round_begin
   bool zpre = false;              // ... and its zero-cost windows were prebuilt (ctx->zwin)
+  bool gcert = false;             // ... and the groups' certificates were written (ctx->gcert)
   bool stage_flag = false;        // the grouped order's counts are signalled by ctx->flag_host
   bool gathered = false;          // ... and group_sort_gather_kernel wrote the gathered order
   bool prep_fused = false;        // build_order's order_scatter_kernel filled placement / zone tables
@@ -177,6 +178,7 @@ struct pvt_ctx {
   int64_t n_epochs = 0, n_segs = 0, n_rejected = 0;
   int64_t n_zchains = 0, n_gchains = 0;   // epoch chains walked by the frontier / list walk
   int64_t n_longest = 0;                  // tasks of the longest epoch chain (sum over epochs)
+  int64_t n_fastpro = 0;                  // frontier chains that took the fast prologue (bit 8 of their word)
   int zwalk = 1;                          // zero-cost frontier walk of epoch chains
   int of_tasks = ORDERED_FRONTIER_TASKS;  // ordered frontier tasks per attempt (PVT_OF_TASKS)
   Buf fwin;                               // host-sharded frontier walks: merged windows
@@ -191,6 +193,7 @@ struct pvt_ctx {
   int t_zpre = 1;                 // PVT_ZPRE: 0 = every frontier walk builds its own window
   int t_chain_tab = 1;            // PVT_CHAIN_TAB: 0 = chain tables uploaded before the walk
   int t_epoch_tail = 1;           // PVT_EPOCH_TAIL: 0 = every frontier-walked epoch runs the tail kernels
+  int t_chain_cert = 1;           // PVT_CHAIN_CERT: 0 = every frontier walk scans its chain's demand rows
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
   int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
   int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
@@ -204,6 +207,7 @@ struct pvt_ctx {
   Buf cmax;                       // frontier-walked epochs: chains' largest demands
   Buf zwin;                       // the first epoch's zero-cost windows (ZoneWindows)
   Buf zundo;                      // frontier walks' optimistic apply: per chain, what undoes it (ZwUndo)
+  Buf gcert;                      // the grouped order's group certificates (GroupCert per group)
   int32_t* ep_host = nullptr;     // pinned staging of ep_dev
   int32_t* ep_hdev = nullptr;     // ep_host's device address (the accept kernel's readback)
   pvt_round* rstage = nullptr;    // pvt_place_batch: descriptors staged for the device (pinned)

@@ -403,11 +403,25 @@ __global__ __launch_bounds__(1024) void epoch_accept_apply_kernel(EpochArgs A, i
 
 // A frontier walk's optimistic apply, taken back (the epoch was not accepted whole): block c, for
 // a chain c that wrote its window back, stores the window's epoch-start rows again (ZwUndo: saved
-// by the walk's prologue; different chains' windows hold disjoint hosts).
+// by the walk's prologue; different chains' windows hold disjoint hosts). A chain of `fast` took
+// the walk's fast prologue and saved nothing: its rows are the first min(n, ZW_M) of the prebuilt
+// window it walked (zpre->w[win.w[c]], which no kernel writes after the order launch).
 __global__ __launch_bounds__(256) void epoch_undo_kernel(const ZwUndo* undo, uint64_t chains,
-                                                         double* avail, int H) {
+                                                         double* avail, int H, uint64_t fast,
+                                                         const ZoneWindows* zpre, UndoWin win) {
   const int c = blockIdx.x;
   if (!((chains >> c) & 1ull)) return;
+  if ((fast >> c) & 1ull) {
+    const ZoneWindow& w = zpre->w[min((int)win.w[c], ZMAX - 1)];
+    const int n = min(max(w.n, 0), ZW_M);
+    for (int p = threadIdx.x; p < n; p += blockDim.x) {
+      const int h = w.id[p];
+      if (h < 0 || h >= H) continue;
+#pragma unroll
+      for (int r = 0; r < 4; r++) avail[(size_t)r * H + h] = w.a[r][p];
+    }
+    return;
+  }
   const ZwUndo& u = undo[c];
   const int n = min(max(u.count, 0), ZW_MBIG);
   for (int p = threadIdx.x; p < n; p += blockDim.x) {
@@ -419,9 +433,11 @@ __global__ __launch_bounds__(256) void epoch_undo_kernel(const ZwUndo* undo, uin
 }
 
 void launch_epoch_undo(const ZwUndo* undo, uint64_t chains, int nchains, double* avail, int H,
-                       hipStream_t st) {
+                       hipStream_t st, uint64_t fast, const ZoneWindows* zpre, const UndoWin* win) {
   if (!chains || nchains <= 0) return;
-  PVT_LAUNCH(epoch_undo_kernel, dim3(nchains), dim3(256), 0, st, undo, chains, avail, H);
+  if (!zpre || !win) fast = 0;
+  PVT_LAUNCH(epoch_undo_kernel, dim3(nchains), dim3(256), 0, st, undo, chains, avail, H, fast, zpre,
+             win ? *win : UndoWin{});
 }
 
 void launch_epoch_accept_apply(const EpochArgs& a, int32_t* res, int nchains, hipStream_t st,

@@ -248,8 +248,12 @@ void launch_epoch_accept_apply(const EpochArgs& a, int32_t* res, int nchains, hi
                                int32_t* hout = nullptr, int nwords = 0);
 // a missed optimistic apply of the frontier walk (ZwalkArgs.undo): the chains of `chains` (bit c:
 // chain c wrote its window back) get their windows' epoch-start rows again
+// (chains of `fast` took the fast prologue: their start rows are those of the prebuilt window
+// zpre->w[win.w[c]], which nothing modifies before the verdict)
+struct UndoWin { uint8_t w[64]; };
 void launch_epoch_undo(const struct ZwUndo* undo, uint64_t chains, int nchains, double* avail, int H,
-                       hipStream_t st);
+                       hipStream_t st, uint64_t fast = 0, const struct ZoneWindows* zpre = nullptr,
+                       const UndoWin* win = nullptr);
 void launch_commit_chains(const CommitArgs& a, int nchains, hipStream_t st);
 // vbp best-fit windows: the one-wave list walk with list cursors (pvt_lwalk.hip); CommitArgs as
 // for launch_commit (no epochs, no stamps). status[0] < nt: refill there (0: the list walk decides)
@@ -280,6 +284,35 @@ struct ChainTab {
   int32_t* o_seg_chain;
   int32_t* o_seg_cstart;
   int32_t* o_coff;
+};
+// Group certificates (written by group_sort_gather_kernel's group blocks, one record per group)
+// and what the host knows of an epoch's chains, by value: together they replace the frontier
+// walk's pass over the chain's demand rows and anchors (the fast prologue, pvt_zwalk.hip). A
+// record's sub-batch j covers the group's sorted tasks [64 j, 64 j + 64).
+constexpr int GC_SUB = 4096 / 64;          // (GSORT_MAX / 64, asserted below)
+struct GroupCert {
+  double mx[4], mn[4];    // per-dimension extremes of the group's demands
+  int32_t bad;            // 1: some |d| is not <= 2^500 (NaN included); 2: no record (n > GSORT_MAX)
+  int32_t n;              // tasks
+  int32_t pad[2];
+  double smin[GC_SUB][4]; // per-dimension minima of each sub-batch
+};
+// fast = 1: every segment of the epoch is a whole group with a record and an anchor in [0, Z),
+// the epoch is the round's first (ZwalkArgs.zpre) and every chain has at most ZW_ENT (segment,
+// sub-batch) entries. Segment k: its group's record rec[seg_grp[k]], its first entry's index
+// seg_ent[k] among its chain's entries (chain order). Chain c: its zone set cu[c] (the union of
+// its anchors' zero-cost zones, from the cost table as the device computes it), the prebuilt
+// window cwin[c] of its component (ZoneWindows: the component's lowest zone) and its entry
+// count cent[c].
+constexpr int ZW_ENT = 64;
+struct ChainCert {
+  int32_t fast;
+  const GroupCert* rec;
+  uint32_t cu[CT_SEGS];
+  uint8_t seg_grp[CT_SEGS];
+  uint8_t seg_ent[CT_SEGS];
+  uint8_t cwin[CT_SEGS];
+  uint8_t cent[CT_SEGS];
 };
 struct ZwalkArgs {
   const double* avail;    // epoch-start capacities [4][H]
@@ -320,12 +353,16 @@ struct ZwalkArgs {
   // chain first saves its window's hosts and start capacities in undo[b], and reports status[0],
   // status[1] also to hstat[2b], hstat[2b + 1] and its certificate word to hcert[b] (both mapped
   // pinned): bits 0-3 the dimensions no task of the chain demands (every d[r] is +-0), bits 4-7
-  // the dimensions whose host minimum is at least 2^-287 (best-fit; first-fit reports 0)
+  // the dimensions whose host minimum is at least 2^-287 (best-fit; first-fit reports 0), bit 8
+  // (ZW_CERT_FAST) the chain took the fast prologue: it saved nothing in undo[b], its start rows
+  // are the prebuilt window's (cert.cwin[b]). hcert alone may be set (cert.fast without undo).
   struct ZwUndo* undo;
   int32_t* hstat;
   int32_t* hcert;
   ChainTab tab;           // chain mode: the epoch's chain tables by value (tab.nch > 0), or none
+  ChainCert cert;         // chain mode: cert.fast = the fast prologue (launch_zwalk), or none
 };
+constexpr int ZW_CERT_FAST = 1 << 8;
 constexpr int ZW_MIN_PARTS = 256;
 // per-dimension minima of avail over hosts [lo, hi) into part[ZW_MIN_PARTS][4]
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);
@@ -652,7 +689,9 @@ struct GatherOut {
   uint64_t* stamps;           // diagnostic builds only (PVT_STAMPS): block 0's phases, [16, 20)
   const int32_t* zone;        // zwin != NULL: Z more blocks prebuild the first epoch's zero-cost
   struct ZoneWindows* zwin;   //   windows from the snapshot (ZoneWindows), or NULL
+  struct GroupCert* gcert;    // [G] group certificates written by the groups' blocks, or NULL
 };
+static_assert(GC_SUB * 64 == GSORT_MAX, "a group record holds every sub-batch of a sorted group");
 void launch_group_sort_gather(const PrepArgs& a, const GatherOut& o, hipStream_t st);
 // bytes (rounded up to 16; both buffers 16-B aligned and that long) from mapped pinned memory
 void launch_upload(const void* src_mapped, void* dst, size_t bytes, hipStream_t st);

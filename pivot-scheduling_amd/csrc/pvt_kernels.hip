@@ -1549,6 +1549,7 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
   }
   __syncthreads();
   const int n = fill;
+  if (n > GSORT_MAX && tid == 0 && O.gcert) { O.gcert[g].bad = 2; O.gcert[g].n = n; }   // (no record)
   if (n > GSORT_MAX || n <= 0) return;
   for (int q = tid; q < n; q += 1024) {       // the collected tasks' sort keys
     uint64_t key = 0;
@@ -1566,14 +1567,59 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
   GSTAMP(2);
   const int a = below_s;
   const int32_t anc = A.ganc[g];
-  for (int i = tid; i < n; i += 1024) {
-    const int p = a + i, t = v[i];
-    O.ord[p] = t;
-    if (O.order_out) O.order_out[p] = t;
-    double* o = O.dem_ord + (size_t)p * 4;
-    o[0] = A.dem[t]; o[1] = A.dem[(size_t)T + t]; o[2] = A.dem[2 * (size_t)T + t]; o[3] = A.dem[3 * (size_t)T + t];
-    O.anc_ord[p] = anc;
-    O.grp_ord[p] = g;
+  // The group's certificate (GroupCert) from the rows this loop holds anyway: a wave's 64 lanes of
+  // one pass are the sorted sub-batch (i0 >> 6) + wave, whose per-dimension minima it reduces; the
+  // group's extremes and its bound flag are folded per thread and reduced once after the loop.
+  // A dimension in which the wave's lanes all hold one bit pattern (the trace's disk and gpus: +0
+  // everywhere; sorted order puts equal rows side by side) needs no reduction: lanes past n take
+  // lane 0's row, which is always a task's.
+  GroupCert* const gc = O.gcert ? O.gcert + g : nullptr;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  double gmx[4] = {-DINF, -DINF, -DINF, -DINF}, gmn[4] = {DINF, DINF, DINF, DINF};
+  bool gbad = false;
+  for (int i0 = 0; i0 < n; i0 += 1024) {
+    const int i = i0 + tid;
+    double d[4] = {0.0, 0.0, 0.0, 0.0};
+    if (i < n) {
+      const int p = a + i, t = v[i];
+      O.ord[p] = t;
+      if (O.order_out) O.order_out[p] = t;
+      double* o = O.dem_ord + (size_t)p * 4;
+      d[0] = A.dem[t]; d[1] = A.dem[(size_t)T + t]; d[2] = A.dem[2 * (size_t)T + t]; d[3] = A.dem[3 * (size_t)T + t];
+      o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
+      O.anc_ord[p] = anc;
+      O.grp_ord[p] = g;
+    }
+    if (gc && i0 + wave * 64 < n) {           // (uniform: the wave holds a sub-batch)
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const double f = readlane_d(d[r], 0);
+        const double x = i < n ? d[r] : f;
+        gbad |= !(__builtin_fabs(x) <= 0x1p500);
+        gmx[r] = fmax(gmx[r], x);
+        double m = f;
+        if (__ballot(__double_as_longlong(x) != __double_as_longlong(f)) != 0) m = wave_min_d(x);
+        gmn[r] = fmin(gmn[r], m);
+        if (lane == 0) gc->smin[(i0 >> 6) + wave][r] = m;
+      }
+    }
+  }
+  if (gc) {
+    double* red = reinterpret_cast<double*>(k);   // (the sort is over: k is free)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const double f = readlane_d(gmx[r], 0);     // (a wave without tasks: -inf in every lane)
+      double m = f;
+      if (__ballot(__double_as_longlong(gmx[r]) != __double_as_longlong(f)) != 0) m = wave_max_d(gmx[r]);
+      if (lane == 0) { red[wave * 8 + r] = m; red[wave * 8 + 4 + r] = gmn[r]; }
+    }
+    gbad = __syncthreads_or(gbad);
+    if (tid < 8) {
+      double x = red[tid];
+      for (int w = 1; w < 16; w++) x = tid < 4 ? fmax(x, red[w * 8 + tid]) : fmin(x, red[w * 8 + tid]);
+      if (tid < 4) gc->mx[tid] = x; else gc->mn[tid - 4] = x;
+    }
+    if (tid == 0) { gc->bad = gbad ? 1 : 0; gc->n = n; }
   }
 #ifdef PVT_STAMPS
   __syncthreads();

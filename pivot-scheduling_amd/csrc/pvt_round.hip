@@ -98,6 +98,7 @@ static int build_order(pvt_ctx* ctx, const pvt_round* r, int32_t** ord_out, bool
   RoundState& R = ctx->rs;
   R.ginfo = false;
   R.zpre = false;
+  R.gcert = false;
   if (grouped && r->n_groups <= (1 << 20)) {
     // one synchronisation: group counts, group anchors and the cost table to the host
     const int G = r->n_groups;
@@ -149,12 +150,17 @@ static int build_order(pvt_ctx* ctx, const pvt_round* r, int32_t** ord_out, bool
         pa.seq = ++ctx->flag_seq;
         R.stage_flag = true;
         const bool zw = hmin && zwin && ca && r->n_zones <= ZMAX;
+        // (the groups' certificates for the first epoch's frontier walk, with its windows)
+        const bool gc = zw && ctx->t_chain_cert;
+        if (gc) ENSURE(ctx->gcert, sizeof(GroupCert) * (size_t)GCOMPACT_MAX);
         launch_group_sort_gather(pa, GatherOut{cur, P<double>(ctx->dem_ord), P<int32_t>(ctx->anc_ord),
                                                P<int32_t>(ctx->grp_ord), r->order, r->avail,
                                                r->n_hosts, hmin, ctx->stamps, r->zone,
-                                               zw ? zwin : nullptr}, st);
+                                               zw ? zwin : nullptr,
+                                               gc ? P<GroupCert>(ctx->gcert) : nullptr}, st);
         if (hmin_done) *hmin_done = hmin != nullptr;
         R.zpre = zw;
+        R.gcert = gc;
         R.gathered = true;
         R.ginfo = ca;
         *pending = true;
@@ -455,6 +461,7 @@ int pvt::round_begin(pvt_ctx* ctx, const pvt_round* rin, int lo, int hi, int wor
     bool redo = false;
     if ((rc = build_order_check(ctx, r, &redo))) return rc;
     if (redo) {
+      R.gcert = false;                        // (a group had no record)
       if ((rc = build_order_radix(ctx, r, &R.ord))) return rc;
       if ((rc = order_out())) return rc;
     }
@@ -1131,7 +1138,7 @@ int pvt::place_windowed(pvt_ctx* ctx, const pvt_round* r) {
   ctx->rs.sharded = false;
   if ((rc = round_begin(ctx, r, 0, r->n_hosts, 1))) return rc;
   ctx->n_epochs = ctx->n_segs = ctx->n_rejected = 0;
-  ctx->n_zchains = ctx->n_gchains = ctx->n_longest = 0;
+  ctx->n_zchains = ctx->n_gchains = ctx->n_longest = ctx->n_fastpro = 0;
   if ((rc = epoch_groups(ctx))) return rc;
   rc = (ctx->rs.egs.empty() || ctx->rs.ffe) ? place_pipelined(ctx) : place_epochs(ctx);
   ctx->rs.active = false;

@@ -169,6 +169,56 @@ static bool chain_tab(pvt_ctx* ctx, const EpochPlan& E, ChainTab& t) {
   return true;
 }
 
+// What the host knows of the first epoch's chains, by value, for the frontier walk's fast prologue
+// (ChainCert, pvt_kernels.h): false unless the grouped order's launch wrote this
+// round's group certificates and every segment is a whole group of at most GSORT_MAX tasks with
+// an anchor in [0, Z). Segment k of an epoch planned from task 0 is the round's k-th non-empty
+// group (epoch_plan). A chain's zone set is the union of its anchors' zero-cost zones, by the
+// expression the device uses (cost[a][z] + cost[z][a] == 0.0); its window is the one
+// zone_window_block built for the lowest zone of its anchors' zero-cost component. uw: the same
+// windows for epoch_undo_kernel.
+static bool chain_cert(pvt_ctx* ctx, int t0, const EpochPlan& E, ChainCert& cc, UndoWin& uw) {
+  const RoundState& R = ctx->rs;
+  const int Z = R.Z, G = R.r.n_groups;
+  const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
+  if (!ctx->t_chain_cert || !R.gcert || !R.ginfo || t0 != 0) return false;
+  if (Z > ZMAX || (int)R.ezcomp.size() != Z || R.cost_host.size() != (size_t)Z * Z) return false;
+  if (G > GCOMPACT_MAX || (int)R.gcnt.size() < G || nseg > CT_SEGS || nch > CT_SEGS) return false;
+  std::vector<int> gids;                      // the non-empty groups, in order
+  for (int g = 0; g < G; g++)
+    if (R.gcnt[g] > 0) gids.push_back(g);
+  if (gids.size() + 1 != R.egs.size() || (int)gids.size() < nseg) return false;
+  std::vector<uint32_t> am(Z, 0u);
+  for (int a = 0; a < Z; a++)
+    for (int z = 0; z < Z; z++)
+      if (R.cost_host[(size_t)a * Z + z] + R.cost_host[(size_t)z * Z + a] == 0.0) am[a] |= 1u << z;
+  cc = ChainCert{};
+  for (int c = 0; c < nch; c++) {
+    int root = -1, ent = 0;
+    uint32_t U = 0;
+    for (int sg : E.segs[c]) {
+      const int len = E.off[sg + 1] - E.off[sg], a = R.ega[sg];
+      if (len != R.gcnt[gids[sg]] || len > GSORT_MAX || a < 0 || a >= Z) return false;
+      if (root >= 0 && R.ezcomp[a] != root) return false;   // (a chain lies in one component)
+      root = R.ezcomp[a];
+      U |= am[a];
+      cc.seg_grp[sg] = (uint8_t)gids[sg];
+      if (ent >= ZW_ENT) return false;
+      cc.seg_ent[sg] = (uint8_t)ent;
+      ent += (len + 63) / 64;
+    }
+    if (root < 0 || ent > ZW_ENT) return false;
+    int j = 0;
+    while (R.ezcomp[j] != root) j++;          // the component's lowest zone
+    cc.cu[c] = U;
+    cc.cwin[c] = uw.w[c] = (uint8_t)j;
+    cc.cent[c] = (uint8_t)ent;
+  }
+  cc.rec = P<GroupCert>(ctx->gcert);
+  cc.fast = 1;
+  return true;
+}
+
 // ---------------------------------------------------------------- the epoch tail
 // A frontier-walked epoch whose chains all walk to their end needs none of the kernels after the
 // walk: each chain writes its window back itself (ZwalkArgs.undo: the optimistic
@@ -237,9 +287,21 @@ static bool tail_accepted(pvt_ctx* ctx, const EpochPlan& E, bool best_fit, uint6
 
 // A missed optimistic apply: the chains that wrote back get their start rows again, before the
 // tail kernels run on the epoch's start state as ever.
-static void tail_undo(pvt_ctx* ctx, uint64_t wrote, int nch) {
+// (fast: the chains that took the fast prologue saved nothing: their rows are those of the
+// prebuilt windows uw they walked)
+static void tail_undo(pvt_ctx* ctx, uint64_t wrote, int nch, uint64_t fast = 0, const UndoWin* uw = nullptr) {
   Scope sc(ctx, PVT_K_OTHER, 0, 0, nullptr, "epoch_undo_kernel");
-  launch_epoch_undo(P<ZwUndo>(ctx->zundo), wrote, nch, ctx->rs.r.avail, ctx->rs.H, ctx->stream);
+  launch_epoch_undo(P<ZwUndo>(ctx->zundo), wrote, nch, ctx->rs.r.avail, ctx->rs.H, ctx->stream, fast,
+                    fast ? P<ZoneWindows>(ctx->zwin) : nullptr, uw);
+}
+
+// The chains whose certificate word reports the fast prologue (counted: pvt_prologue_stats).
+static uint64_t fast_chains(pvt_ctx* ctx, int nch) {
+  uint64_t m = 0;
+  for (int c = 0; c < nch && c < 64; c++)
+    if (ctx->ep_host[EP_CERT + c] & ZW_CERT_FAST) m |= 1ull << c;
+  ctx->n_fastpro += __builtin_popcountll(m);
+  return m;
 }
 
 // The tail kernels, each in a scope of its own name: finality, pair validation (validate), and
@@ -422,7 +484,11 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       // (the first epoch starts from the snapshot the grouped order's launch built its windows from)
       if (R.zpre && t0 == 0 && !big) za.zpre = P<ZoneWindows>(ctx->zwin);
       if (tabv) za.tab = tab;
+      // the fast prologue: the groups' certificates instead of a pass over the chains' rows
+      UndoWin uw{};
+      const bool fastp = tabv && za.zpre && chain_cert(ctx, t0, E, za.cert, uw);
       R.zpre = false;
+      R.gcert = false;
       ea.cmax = P<double>(ctx->cmax);
       ea.coff = dev + EP_COFF;
       ea.nch = nch;
@@ -434,6 +500,9 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       const bool opt = apart && tail_eligible(ctx);
       if (!apart) ea.cmax = nullptr;
       if (opt && (rc = tail_walk_args(ctx, za))) return rc;
+      // (without the optimistic apply the chains' words go to the device, and come back with the
+      // tail's readback)
+      if (fastp && !opt) za.hcert = dev + EP_CERT;
       {
         Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
         if (big) launch_zwalk_big(za, nch, st);
@@ -447,13 +516,14 @@ int pvt::place_epochs(pvt_ctx* ctx) {
         // launch; else the write-backs are undone and the tail decides as ever
         HIPCHK(hipStreamSynchronize(st));
         uint64_t wrote = 0;
+        const uint64_t fastm = fastp ? fast_chains(ctx, nch) : 0;
         if (tail_accepted(ctx, E, true, &wrote)) {
           ctx->n_zchains += nch;
           ctx->n_longest += *std::max_element(E.len.begin(), E.len.end());
           t0 += nt;
           continue;
         }
-        tail_undo(ctx, wrote, nch);
+        tail_undo(ctx, wrote, nch, fastm & wrote, &uw);
       }
       // validation, the accepted prefix and its apply all on the device, then one readback. A
       // chain the frontier walk could not prove is not accepted past its first segment; the
@@ -462,6 +532,7 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       epoch_tail(ctx, ea, true, nch);
       HIPCHK(hipGetLastError());
       HIPCHK(hipStreamSynchronize(st));
+      if (fastp && !opt) (void)fast_chains(ctx, nch);
       int adv = 0;
       if ((rc = epoch_frontier_verdict(ctx, E, t0, &need, &adv))) return rc;
       if (need && adv < nt) {

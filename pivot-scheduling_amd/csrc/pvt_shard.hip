@@ -139,7 +139,7 @@ extern "C" int pvt_shard_begin(pvt_ctx* ctx, const pvt_round* r, int32_t host_lo
   ctx->rs.nt = 0;
   ctx->rs.pkind = PK_LIST;
   ctx->n_epochs = ctx->n_segs = ctx->n_rejected = 0;
-  ctx->n_zchains = ctx->n_gchains = ctx->n_longest = 0;
+  ctx->n_zchains = ctx->n_gchains = ctx->n_longest = ctx->n_fastpro = 0;
   if (ctx->checks) {
     int rc = gate_checks(ctx, r, 1, true, false);
     if (rc) return rc;

@@ -34,7 +34,9 @@
 // holds each of its hosts' final state in its window and writes it to global availability
 // itself; with every chain's report in the host's mapped words, an epoch whose chains all
 // completed needs no kernel after this one. The prologue saves the window's start rows (ZwUndo)
-// for the epochs the host does not accept whole.
+// for the epochs the host does not accept whole; the fast prologue (FAST below: the round's first
+// epoch, from the order launch's group certificates) saves nothing, its start rows are those of
+// the prebuilt window it walks.
 //
 // FF: the same chain walk for cost_aware FIRST-fit with sort_hosts (scheduler/cost_aware.py:
 // 99-127). A group's hosts are taken in the order of the frozen key c*df/(||avail||*bw); hosts
@@ -96,28 +98,6 @@ struct ZwalkLDS {
   int32_t touch[WM / 64];                  // optimistic apply: chunks committed to in LDS (past p0 / pb)
 };
 
-// Wave reductions of doubles, uniform results: DPP row prefix steps (lane 15 of each 16-lane row
-// then holds the row's result), then the four rows by readlane -- no LDS permutes.
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  const uint32_t lo = dpp_u32<CTRL>((uint32_t)b, (uint32_t)b);
-  const uint32_t hi = dpp_u32<CTRL>((uint32_t)(b >> 32), (uint32_t)(b >> 32));
-  return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-template <class Op>
-__device__ __forceinline__ double wave_reduce_d(double v, Op op) {
-  v = op(v, dpp_d<DPP_ROW_SHR1>(v));
-  v = op(v, dpp_d<DPP_ROW_SHR2>(v));
-  v = op(v, dpp_d<DPP_ROW_SHR4>(v));
-  v = op(v, dpp_d<DPP_ROW_SHR8>(v));
-  const double r0 = readlane_d(v, 15), r1 = readlane_d(v, 31);
-  const double r2 = readlane_d(v, 47), r3 = readlane_d(v, 63);
-  return op(op(r0, r1), op(r2, r3));
-}
-__device__ __forceinline__ double wave_max_d(double v) {
-  return wave_reduce_d(v, [](double a, double b) { return fmax(a, b); });
-}
 // NaN-propagating maximum (fmax drops a NaN operand): the FF certificate (2') must fail on a NaN
 // capacity, whose frozen key would break the reference's sorted() order (cost_aware.py:116).
 __device__ __forceinline__ double nan_max(double a, double b) {
@@ -125,9 +105,6 @@ __device__ __forceinline__ double nan_max(double a, double b) {
 }
 __device__ __forceinline__ double wave_nmax_d(double v) {
   return wave_reduce_d(v, [](double a, double b) { return nan_max(a, b); });
-}
-__device__ __forceinline__ double wave_min_d(double v) {
-  return wave_reduce_d(v, [](double a, double b) { return fmin(a, b); });
 }
 
 // Per-dimension minimum capacity over hosts [lo, hi) (certificate 2), ZW_MINB partials.
@@ -235,7 +212,9 @@ __device__ __forceinline__ uint64_t zstamp() {
 // back at the end and status[0] = tasks walked.
 // KEYED with STRICT = false: vbp first-fit (index order, fit >=) over a window of the first
 // alive hosts (the driver's ordered_frontier), same mechanics.
-template <bool KEYED, bool STRICT, bool FF = false, int WM = ZW_M>
+// FAST: the fast prologue of the round's first best-fit epoch (below), a template flag so that
+// neither instance carries both prologues.
+template <bool KEYED, bool STRICT, bool FF = false, int WM = ZW_M, bool FAST = false>
 __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   static_assert(!FF || (!KEYED && STRICT), "FF: chain mode, strict fit");
   static_assert(WM == ZW_M || !KEYED, "keyed / ordered / sharded windows: ZW_M hosts");
@@ -270,317 +249,494 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (!KEYED && A.hstat) { A.hstat[2 * b] = s0; A.hstat[2 * b + 1] = s1; }
   };
 
-  // Every load the prologue needs that depends on nothing else is issued first (the zone
-  // tables, the host minima, the chain's first task positions, its segment range), so the
-  // prologue waits for about two HBM latencies, not one per step.
-  static_assert(ZMAX * ZMAX <= 4 * ZW_THREADS && ZW_MINB == ZW_THREADS, "prologue loads");
-  const int ZZ = KEYED ? 0 : Z * Z;
-  double cs[4], bs[4];
-#pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int i = tid + u * ZW_THREADS;
-    cs[u] = i < ZZ ? A.csum[i] : 0.0;
-    bs[u] = i < ZZ ? A.bsum[i] : 0.0;
-  }
-  // host minima (FF: maxima of |capacity|) from the partials
-  double ha[4] = {FF ? -DINF : DINF, FF ? -DINF : DINF, FF ? -DINF : DINF, FF ? -DINF : DINF};
-  if (!KEYED) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const double x = A.hmin[tid * 4 + r];
-      ha[r] = FF ? nan_max(ha[r], x) : fmin(ha[r], x);
-    }
-  }
-  if (tabm) {
-    int32_t* wmap = const_cast<int32_t*>(A.cmap) + base;
-    for (int k = A.tab.csoff[b]; k < A.tab.csoff[b + 1]; k++) {
-      const int sg = A.tab.csegid[k], c0 = A.tab.seg_cstart[sg], o0 = A.tab.seg_off[sg];
-      const int len = A.tab.seg_off[sg + 1] - o0;
-      for (int i = tid; i < len; i += ZW_THREADS) wmap[c0 + i] = o0 + i;
-    }
-    // block 0 publishes the tables for the epoch kernels after the walk
-    if (b == 0) {
-      const int ns = A.tab.nseg, nc = A.tab.nch;
-      for (int i = tid; i <= ns; i += ZW_THREADS) {
-        A.tab.o_seg_off[i] = A.tab.seg_off[i];
-        if (i < ns) { A.tab.o_seg_chain[i] = A.tab.seg_chain[i]; A.tab.o_seg_cstart[i] = A.tab.seg_cstart[i]; }
+  // the chain's range of the position map from the segments, and block 0's publication of the
+  // tables for the epoch kernels after the walk (tables by value; either prologue)
+  auto publish_map = [&]() {
+    if (tabm) {
+      int32_t* wmap = const_cast<int32_t*>(A.cmap) + base;
+      for (int k = A.tab.csoff[b]; k < A.tab.csoff[b + 1]; k++) {
+        const int sg = A.tab.csegid[k], c0 = A.tab.seg_cstart[sg], o0 = A.tab.seg_off[sg];
+        const int len = A.tab.seg_off[sg + 1] - o0;
+        for (int i = tid; i < len; i += ZW_THREADS) wmap[c0 + i] = o0 + i;
       }
-      for (int i = tid; i <= nc; i += ZW_THREADS) A.tab.o_coff[i] = A.tab.coff[i];
+      // block 0 publishes the tables for the epoch kernels after the walk
+      if (b == 0) {
+        const int ns = A.tab.nseg, nc = A.tab.nch;
+        for (int i = tid; i <= ns; i += ZW_THREADS) {
+          A.tab.o_seg_off[i] = A.tab.seg_off[i];
+          if (i < ns) { A.tab.o_seg_chain[i] = A.tab.seg_chain[i]; A.tab.o_seg_cstart[i] = A.tab.seg_cstart[i]; }
+        }
+        for (int i = tid; i <= nc; i += ZW_THREADS) A.tab.o_coff[i] = A.tab.coff[i];
+      }
     }
-  }
-  int wv[ZW_PR];
-  if (tabm) {
-    // the first positions straight from the segments (no dependent load of the map before the
-    // demand rows: one HBM latency less in the prologue)
+  };
+  double mn[4];                              // (the walk: the batch's minima ahead)
+  uint32_t U;                                // the window's zone set (certificate 2)
+  int nwin;
+#ifdef PVT_STAMPS
+  uint64_t t_load, t_cert, t_win, t_cap;
+#endif
+  if constexpr (FAST) {
+    // ---- The fast prologue (ChainCert): an unsharded best-fit chain of the
+    // round's first epoch, tables by value, every segment a whole group with a certificate
+    // (GroupCert) from the order launch, its window prebuilt (ZoneWindows). Every load is issued
+    // here, before the first barrier, all in flight together: the zone tables, the host-minimum
+    // partials, the window the host names (its zone set, n, bad, ids, zones, capacities, straight
+    // to LDS) and the records of this chain's segments -- wave w takes segments w, w + 4, ..., a
+    // lane per 64-task sub-batch. No pass over demand rows or anchors, no finiteness scan of the
+    // capacities (ZoneWindow::bad), no ZwUndo stores (epoch_undo_kernel reads the window itself).
+    // Exactness:
+    //  * extremes, bound flag: fmax / fmin over the records equal the scan's over the rows (fmax
+    //    and fmin drop a NaN either way) up to the sign of a zero, which no consumer distinguishes
+    //    (the certificate word and sep compare with <=, >=; cmax is only subtracted from);
+    //  * window: the host's zone set of the chain must lie in the window's U' (else (0, 1): the
+    //    list walk decides); U' takes U's place in certificate 2, as in the other prologue;
+    //  * batch minima: S.smin[q] is the minimum over the (segment, sub-batch) entries, in chain
+    //    order, from the first whose chain-local range reaches past 64 q -- a lower bound of the
+    //    demands at positions >= 64 q (a straddling sub-batch brings up to 63 earlier tasks). The
+    //    walk uses it (mn) only to decide that a chunk can still take a task ahead, so a lower
+    //    bound only keeps a chunk alive longer; slots no entry owns stay at -inf.
+    static_assert(!KEYED && !FF && WM == ZW_M && ZW_M == 4 * ZW_THREADS, "fast prologue: best-fit chains");
+    static_assert(ZW_ENT <= 64 && ZW_ENT <= ZW_SB, "entries: a lane each, in rwho / rstart / lg");
+    const int j = min((int)A.cert.cwin[b], ZMAX - 1);
+    const ZoneWindow* const zw = &A.zpre->w[j];
+    const int ZZ = Z * Z;
+    double cs[4], bs[4], ha[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = tid + u * ZW_THREADS;
+      cs[u] = i < ZZ ? A.csum[i] : 0.0;
+      bs[u] = i < ZZ ? A.bsum[i] : 0.0;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) ha[r] = A.hmin[tid * 4 + r];
+    const uint32_t zu = A.zpre->U[j];
+    const int zn = zw->n, zbad = zw->bad;
+    int32_t wi[4], wzv[4];
+    double wv[4][4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int p = tid + u * ZW_THREADS;
+      wi[u] = zw->id[p];
+      wzv[u] = zw->z[p];
+#pragma unroll
+      for (int r = 0; r < 4; r++) wv[u][r] = zw->a[r][p];
+    }
     const int k0 = A.tab.csoff[b], k1 = A.tab.csoff[b + 1];
+    // a segment's record: lane l its sub-batch l's minima, lanes 0-3 the maxima; entries at
+    // seg_ent + l of the chain's list (values in S.lg, chain-local range in S.rstart / S.rwho)
+    double mxv = -DINF;
+    bool badv = false;
+    for (int k = k0 + wave; k < k1; k += ZW_WAVES) {
+      const int sg = A.tab.csegid[k], c0 = A.tab.seg_cstart[sg];
+      const int len = A.tab.seg_off[sg + 1] - A.tab.seg_off[sg];
+      const GroupCert* const gc = A.cert.rec + min((int)A.cert.seg_grp[sg], GCOMPACT_MAX - 1);
+      const int ne = (len + 63) >> 6, e = A.cert.seg_ent[sg] + lane;
+      const bool on = lane < ne && lane < GC_SUB && e < ZW_ENT;
+      double sm[4];
 #pragma unroll
-    for (int u = 0; u < ZW_PR; u++) {
-      const int i = u * ZW_THREADS + tid;
-      int v = -1;
-      for (int k = k0; k < k1; k++) {
-        const int sg = A.tab.csegid[k], c0 = A.tab.seg_cstart[sg];
-        if (i >= c0) v = A.tab.seg_off[sg] + (i - c0);
+      for (int r = 0; r < 4; r++) sm[r] = on ? gc->smin[lane][r] : DINF;
+      const double gm = lane < 4 ? gc->mx[lane] : -DINF;
+      badv |= gc->bad != 0 || gc->n != len;
+      mxv = fmax(mxv, gm);
+      if (on) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) S.lg[e][r] = sm[r];
+        S.rstart[e] = c0 + 64 * lane;
+        S.rwho[e] = c0 + min(64 * lane + 64, len);
       }
-      wv[u] = i < nt ? v : -1;
     }
-  } else {
+    publish_map();
 #pragma unroll
-    for (int u = 0; u < ZW_PR; u++) {
-      const int i = u * ZW_THREADS + tid;
-      wv[u] = i < nt ? (KEYED ? i : gcmap[i]) : -1;
+    for (int u = 0; u < 4; u++) {
+      const int i = tid + u * ZW_THREADS;
+      if (i < ZZ) { S.csum[i] = cs[u]; S.bsum[i] = bs[u]; }
     }
-  }
-  const int sg0 = tabm ? A.tab.csoff[b] : (!KEYED && A.cseg) ? A.csoff[b] : 0;
-  const int sg1 = tabm ? A.tab.csoff[b + 1] : (!KEYED && A.cseg) ? A.csoff[b + 1] : 0;
-  // prebuilt windows' zone sets (ZoneWindows; lane j: zone j's, 0 = none)
-  const uint32_t zpu = (!KEYED && WM == ZW_M && A.zpre && lane < Z) ? A.zpre->U[lane] : 0u;
-
+    if (tid < CHAIN_MAX / 64) S.sbits[tid] = 0;
+    if (tid < WM / 64) S.touch[tid] = 0;
+    if (tid < ZW_SB) {
 #pragma unroll
-  for (int u = 0; u < 4; u++) {
-    const int i = tid + u * ZW_THREADS;
-    if (i < ZZ) { S.csum[i] = cs[u]; S.bsum[i] = bs[u]; }
-  }
-  if (tid == 0) { S.umask = 0; S.nwin = 0; S.bail = 0; }
-  if (tid < CHAIN_MAX / 64) S.sbits[tid] = 0;
-  if (tid < WM / 64) S.touch[tid] = 0;
-  __syncthreads();
-  if (!KEYED && tid < Z) {                   // anchor row -> zero-cost zone mask
-    uint32_t m = 0;
-    for (int z = 0; z < Z; z++) m |= (S.csum[tid * Z + z] == 0.0) ? (1u << z) : 0u;
-    S.amask[tid] = m;
-  }
-  if (tabm) {                                // segment starts (chain-local positions)
-    for (int k = sg0 + tid; k < sg1; k += ZW_THREADS) {
+      for (int r = 0; r < 4; r++) S.smin[tid][r] = -DINF;
+    }
+    nwin = min(zn, ZW_M);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int p = tid + u * ZW_THREADS;
+      if (p < nwin) {
+        S.wid[p] = wi[u];
+        S.wz[p] = wzv[u];
+#pragma unroll
+        for (int r = 0; r < 4; r++) S.wa[r][p] = wv[u][r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) ha[r] = wave_min_d(ha[r]);
+    const bool wbadv = __ballot(badv) != 0;
+    if (lane < 4) S.red[wave][lane] = mxv;
+    if (lane == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) S.red[wave][8 + r] = ha[r];
+      S.cnt[0][wave] = wbadv ? 1 : 0;
+    }
+#ifdef PVT_STAMPS
+    t_load = zstamp();
+#endif
+    __syncthreads();
+    if (tid < Z) {                             // anchor row -> zero-cost zone mask
+      uint32_t m = 0;
+      for (int z = 0; z < Z; z++) m |= (S.csum[tid * Z + z] == 0.0) ? (1u << z) : 0u;
+      S.amask[tid] = m;
+    }
+    for (int k = k0 + tid; k < k1; k += ZW_THREADS) {   // segment starts (chain-local positions)
       const int p = A.tab.seg_cstart[A.tab.csegid[k]];
       if (p > 0 && p < CHAIN_MAX) atomicOr(&S.sbits[p >> 6], 1ull << (p & 63));
     }
+    double mx[4];
+    bool bad = false;
+#pragma unroll
+    for (int w = 0; w < ZW_WAVES; w++) bad |= S.cnt[0][w] != 0;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      mx[r] = fmax(fmax(S.red[0][r], S.red[1][r]), fmax(S.red[2][r], S.red[3][r]));
+      ha[r] = fmin(fmin(S.red[0][8 + r], S.red[1][8 + r]), fmin(S.red[2][8 + r], S.red[3][8 + r]));
+    }
+    // the entries' suffix minima, wave r for dimension r, a lane per entry; an entry owns the
+    // slot q whose boundary 64 q lies in its range [start, end) (at most one: 64 tasks or fewer)
+    const int ne = min((int)A.cert.cent[b], ZW_ENT);
+    {
+      double v = lane < ne ? S.lg[lane][wave] : DINF;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) v = fmin(v, __shfl_down(v, off));
+      if (lane < ne) {
+        const int q = (S.rstart[lane] + 63) >> 6;
+        if (q * 64 < S.rwho[lane] && q < ZW_SB) S.smin[q][wave] = v;
+      }
+      if (lane == 0) S.red[0][4 + wave] = v;   // (the chain's minimum: the certificate word)
+    }
+    bool sep = false;
+#pragma unroll
+    for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= 0x1p-288);
+    U = zu;
+    // (it never walks a window it has not verified: the host's zone set inside the window's)
+    const bool cover = zu != 0 && (A.cert.cu[b] & ~zu) == 0;
+    const bool stop = bad || !sep || nt <= 0 || nt > CHAIN_MAX || !cover || zbad != 0 || nwin <= 0;
+#ifdef PVT_STAMPS
+    t_cert = t_win = t_cap = zstamp();
+#endif
+    __syncthreads();
+    if (tid == 0) {
+      int cert = stop ? 0 : ZW_CERT_FAST;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const double mnr = S.red[0][4 + r];
+        cert |= ((mx[r] <= 0.0 && mnr >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
+      }
+      if (A.hcert) A.hcert[b] = cert;
+      if (stop) report(0, nt <= 0 ? 0 : 1);
+    }
+    if (A.cmax && tid < 4) A.cmax[b * 4 + tid] = mx[tid];   // (the validation's fast path)
+    if (stop) return;
   } else {
-    for (int k = sg0 + tid; k < sg1; k += ZW_THREADS) {
-      const int p = A.cseg[k];
-      if (p > 0 && p < CHAIN_MAX) atomicOr(&S.sbits[p >> 6], 1ull << (p & 63));
+    // Every load the prologue needs that depends on nothing else is issued first (the zone
+    // tables, the host minima, the chain's first task positions, its segment range), so the
+    // prologue waits for about two HBM latencies, not one per step.
+    static_assert(ZMAX * ZMAX <= 4 * ZW_THREADS && ZW_MINB == ZW_THREADS, "prologue loads");
+    const int ZZ = KEYED ? 0 : Z * Z;
+    double cs[4], bs[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int i = tid + u * ZW_THREADS;
+      cs[u] = i < ZZ ? A.csum[i] : 0.0;
+      bs[u] = i < ZZ ? A.bsum[i] : 0.0;
     }
-  }
+    // host minima (FF: maxima of |capacity|) from the partials
+    double ha[4] = {FF ? -DINF : DINF, FF ? -DINF : DINF, FF ? -DINF : DINF, FF ? -DINF : DINF};
+    if (!KEYED) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const double x = A.hmin[tid * 4 + r];
+        ha[r] = FF ? nan_max(ha[r], x) : fmin(ha[r], x);
+      }
+    }
+    publish_map();
+    int wv[ZW_PR];
+    if (tabm) {
+      // the first positions straight from the segments (no dependent load of the map before the
+      // demand rows: one HBM latency less in the prologue)
+      const int k0 = A.tab.csoff[b], k1 = A.tab.csoff[b + 1];
+#pragma unroll
+      for (int u = 0; u < ZW_PR; u++) {
+        const int i = u * ZW_THREADS + tid;
+        int v = -1;
+        for (int k = k0; k < k1; k++) {
+          const int sg = A.tab.csegid[k], c0 = A.tab.seg_cstart[sg];
+          if (i >= c0) v = A.tab.seg_off[sg] + (i - c0);
+        }
+        wv[u] = i < nt ? v : -1;
+      }
+    } else {
+#pragma unroll
+      for (int u = 0; u < ZW_PR; u++) {
+        const int i = u * ZW_THREADS + tid;
+        wv[u] = i < nt ? (KEYED ? i : gcmap[i]) : -1;
+      }
+    }
+    const int sg0 = tabm ? A.tab.csoff[b] : (!KEYED && A.cseg) ? A.csoff[b] : 0;
+    const int sg1 = tabm ? A.tab.csoff[b + 1] : (!KEYED && A.cseg) ? A.csoff[b + 1] : 0;
+    // prebuilt windows' zone sets (ZoneWindows; lane j: zone j's, 0 = none)
+    const uint32_t zpu = (!KEYED && WM == ZW_M && A.zpre && lane < Z) ? A.zpre->U[lane] : 0u;
 
-  // the chain's anchors (-> its zones U below), demand extremes and finiteness (certificates 2,
-  // 3), and the minima of the demands per 64-task batch (for the suffix minima below: a wave's
-  // 64 lanes of one pass are one batch); ZW_PR rows per thread in flight at once, the next pass's
-  // positions loaded while this one is reduced
-  uint32_t abits = 0;                        // anchors seen (Z <= 32)
-  double mx[4] = {-DINF, -DINF, -DINF, -DINF}, mn[4] = {DINF, DINF, DINF, DINF};
-  bool bad = false;
-  for (int i0 = 0; i0 < nt; i0 += ZW_PR * ZW_THREADS) {
-    int av[ZW_PR], wn[ZW_PR];
-    double dv[ZW_PR][4];
 #pragma unroll
-    for (int u = 0; u < ZW_PR; u++) {
-      const int w = max(wv[u], 0);
-      av[u] = A.anc[w];
-#pragma unroll
-      for (int r = 0; r < 4; r++) dv[u][r] = A.dem[(size_t)w * 4 + r];
+    for (int u = 0; u < 4; u++) {
+      const int i = tid + u * ZW_THREADS;
+      if (i < ZZ) { S.csum[i] = cs[u]; S.bsum[i] = bs[u]; }
     }
-#pragma unroll
-    for (int u = 0; u < ZW_PR; u++) {
-      const int i = i0 + ZW_PR * ZW_THREADS + u * ZW_THREADS + tid;
-      wn[u] = i < nt ? (KEYED ? i : cmap_at(i)) : -1;
+    if (tid == 0) { S.umask = 0; S.nwin = 0; S.bail = 0; }
+    if (tid < CHAIN_MAX / 64) S.sbits[tid] = 0;
+    if (tid < WM / 64) S.touch[tid] = 0;
+#ifdef PVT_STAMPS
+    t_load = zstamp();
+#endif
+    __syncthreads();
+    if (!KEYED && tid < Z) {                   // anchor row -> zero-cost zone mask
+      uint32_t m = 0;
+      for (int z = 0; z < Z; z++) m |= (S.csum[tid * Z + z] == 0.0) ? (1u << z) : 0u;
+      S.amask[tid] = m;
     }
+    if (tabm) {                                // segment starts (chain-local positions)
+      for (int k = sg0 + tid; k < sg1; k += ZW_THREADS) {
+        const int p = A.tab.seg_cstart[A.tab.csegid[k]];
+        if (p > 0 && p < CHAIN_MAX) atomicOr(&S.sbits[p >> 6], 1ull << (p & 63));
+      }
+    } else {
+      for (int k = sg0 + tid; k < sg1; k += ZW_THREADS) {
+        const int p = A.cseg[k];
+        if (p > 0 && p < CHAIN_MAX) atomicOr(&S.sbits[p >> 6], 1ull << (p & 63));
+      }
+    }
+
+    // the chain's anchors (-> its zones U below), demand extremes and finiteness (certificates 2,
+    // 3), and the minima of the demands per 64-task batch (for the suffix minima below: a wave's
+    // 64 lanes of one pass are one batch); ZW_PR rows per thread in flight at once, the next pass's
+    // positions loaded while this one is reduced
+    uint32_t abits = 0;                        // anchors seen (Z <= 32)
+    double mx[4] = {-DINF, -DINF, -DINF, -DINF};
+    mn[0] = mn[1] = mn[2] = mn[3] = DINF;
+    bool bad = false;
+    for (int i0 = 0; i0 < nt; i0 += ZW_PR * ZW_THREADS) {
+      int av[ZW_PR], wn[ZW_PR];
+      double dv[ZW_PR][4];
 #pragma unroll
-    for (int u = 0; u < ZW_PR; u++) {
-      const bool ok = wv[u] >= 0;
-      double bm[4];
+      for (int u = 0; u < ZW_PR; u++) {
+        const int w = max(wv[u], 0);
+        av[u] = A.anc[w];
 #pragma unroll
-      for (int r = 0; r < 4; r++) bm[r] = ok ? dv[u][r] : DINF;
-      if (ok) {
-        const int a = av[u];
-        if (a < 0 || a >= Z) {
-          bad = true;
-        } else {
-          abits |= 1u << a;
+        for (int r = 0; r < 4; r++) dv[u][r] = A.dem[(size_t)w * 4 + r];
+      }
 #pragma unroll
-          for (int r = 0; r < 4; r++) {
-            bad |= !(__builtin_fabs(dv[u][r]) <= ZW_BIG);
-            mx[r] = fmax(mx[r], dv[u][r]);
-            mn[r] = fmin(mn[r], dv[u][r]);
+      for (int u = 0; u < ZW_PR; u++) {
+        const int i = i0 + ZW_PR * ZW_THREADS + u * ZW_THREADS + tid;
+        wn[u] = i < nt ? (KEYED ? i : cmap_at(i)) : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < ZW_PR; u++) {
+        const bool ok = wv[u] >= 0;
+        double bm[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) bm[r] = ok ? dv[u][r] : DINF;
+        if (ok) {
+          const int a = av[u];
+          if (a < 0 || a >= Z) {
+            bad = true;
+          } else {
+            abits |= 1u << a;
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+              bad |= !(__builtin_fabs(dv[u][r]) <= ZW_BIG);
+              mx[r] = fmax(mx[r], dv[u][r]);
+              mn[r] = fmin(mn[r], dv[u][r]);
+            }
+          }
+        }
+        const int blk = (i0 + u * ZW_THREADS) / 64 + wave;   // (uniform: the wave's batch)
+        if (blk < ZW_SB - 1 && blk * 64 < nt) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) bm[r] = wave_min_d(bm[r]);
+          if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; r++) S.smin[blk][r] = bm[r];
           }
         }
       }
-      const int blk = (i0 + u * ZW_THREADS) / 64 + wave;   // (uniform: the wave's batch)
-      if (blk < ZW_SB - 1 && blk * 64 < nt) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) bm[r] = wave_min_d(bm[r]);
-        if (lane == 0) {
-#pragma unroll
-          for (int r = 0; r < 4; r++) S.smin[blk][r] = bm[r];
-        }
-      }
+      for (int u = 0; u < ZW_PR; u++) wv[u] = wn[u];
     }
+    __syncthreads();                           // (amask)
+    uint32_t um = 0;
+    if (!KEYED)
+      for (uint32_t m = abits; m; m &= m - 1) um |= S.amask[__builtin_ctz(m)];
 #pragma unroll
-    for (int u = 0; u < ZW_PR; u++) wv[u] = wn[u];
-  }
-  __syncthreads();                           // (amask)
-  uint32_t um = 0;
-  if (!KEYED)
-    for (uint32_t m = abits; m; m &= m - 1) um |= S.amask[__builtin_ctz(m)];
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    mx[r] = wave_max_d(mx[r]);
-    mn[r] = wave_min_d(mn[r]);
-    ha[r] = FF ? wave_nmax_d(ha[r]) : wave_min_d(ha[r]);
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) { S.red[wave][r] = mx[r]; S.red[wave][4 + r] = mn[r]; S.red[wave][8 + r] = ha[r]; }
-  }
-  if (bad) S.bail = 1;                        // benign race: every writer stores 1
-  if (um) atomicOr(&S.umask, um);
-  __syncthreads();
-#ifdef PVT_STAMPS
-  const uint64_t t_cert = zstamp();
-#endif
-#pragma unroll
-  for (int r = 0; r < 4; r++) {
-    for (int w = 1; w < ZW_WAVES; w++) {
-      mx[r] = fmax(mx[r], S.red[w][r]);
-      mn[r] = fmin(mn[r], S.red[w][4 + r]);
-      ha[r] = FF ? nan_max(ha[r], S.red[w][8 + r]) : fmin(ha[r], S.red[w][8 + r]);
+    for (int r = 0; r < 4; r++) {
+      mx[r] = wave_max_d(mx[r]);
+      mn[r] = wave_min_d(mn[r]);
+      ha[r] = FF ? wave_nmax_d(ha[r]) : wave_min_d(ha[r]);
     }
-    mx[r] = fmax(mx[r], S.red[0][r]);
-    mn[r] = fmin(mn[r], S.red[0][4 + r]);
-    ha[r] = FF ? nan_max(ha[r], S.red[0][8 + r]) : fmin(ha[r], S.red[0][8 + r]);
-  }
-  if (!KEYED && A.cmax && tid < 4) A.cmax[b * 4 + tid] = mx[tid];   // (the validation's fast path)
-  if (!KEYED && A.hcert && tid == 0) {       // the certificate word of the host's verdict
-    int cert = 0;
-    if (!FF) {
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        cert |= ((mx[r] <= 0.0 && mn[r] >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
-    }
-    A.hcert[b] = cert;
-  }
-  bool sep = KEYED;
-  if (FF) {                                  // certificates (2') and (3'): bounded capacities,
-    sep = true;                              // demands >= 0
-#pragma unroll
-    for (int r = 0; r < 4; r++) sep &= (ha[r] <= 0x1p298) && (mn[r] >= 0.0);
-  } else {
-#pragma unroll
-    for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= 0x1p-288);
-  }
-  uint32_t U = S.umask;
-  if (S.bail || !sep || nt <= 0 || (!KEYED && nt > CHAIN_MAX)) {
-    if (tid == 0) report(0, (KEYED || nt <= 0) ? 0 : 1);
-    return;
-  }
-  const FrontierSlot* pw = A.pwin ? A.pwin + (KEYED ? 0 : b) : nullptr;
-  // the round's first epoch: the window the grouped order's launch prebuilt for the component of
-  // the chain's anchors (its zone set U' covers U; a window over U' is exact, with U' in the
-  // certificates)
-  const ZoneWindow* zw = nullptr;
-  if (!KEYED && WM == ZW_M && !pw && A.zpre && U != 0) {
-    const uint64_t cover = __ballot(zpu != 0 && (U & ~zpu) == 0);
-    if (cover) {
-      const int j = __builtin_ctzll(cover);
-      zw = &A.zpre->w[j];
-      U = (uint32_t)__builtin_amdgcn_readlane((int)zpu, j);
-    }
-  }
-  if (pw) {                                  // host-sharded: the merged window, capacities too
-    const int nw = min(pw->n, ZW_M);
-    for (int p = tid; p < nw; p += ZW_THREADS) {
-      const int32_t h = pw->id[p];
-      S.wid[p] = h;
-      S.wz[p] = KEYED ? 0 : A.zone[h];
-    }
-    if (tid == 0) S.nwin = nw;
-    __syncthreads();
-  } else if (zw) {                           // prebuilt: ids and zones (capacities below)
-    const int nw = min(zw->n, ZW_M);
-    for (int p = tid; p < nw; p += ZW_THREADS) { S.wid[p] = zw->id[p]; S.wz[p] = zw->z[p]; }
-    if (tid == 0) S.nwin = nw;
-    __syncthreads();
-  } else if (KEYED) {                        // window: the zero-key prefix's first hosts
-    const int nw = min(A.kn_dev ? *A.kn_dev : A.kn, ZW_M);
-    for (int p = tid; p < nw; p += ZW_THREADS) { S.wid[p] = A.lo + A.kperm[p]; S.wz[p] = 0; }
-    if (tid == 0) S.nwin = nw;
-    __syncthreads();
-  } else {                                   // window: U's hosts in index order
-    compact_zone_window<WM>(A.zone, Z, U, 0, H, S.wid, S.wz, S.cnt, &S.nwin);
-  }
-  const int nwin = S.nwin;
-#ifdef PVT_STAMPS
-  const uint64_t t_win = zstamp();
-#endif
-  bool wbad = false;
-  // optimistic apply: the window's hosts and start capacities, saved for an undo (plain stores
-  // nothing waits for)
-  ZwUndo* const ud = (!KEYED && A.undo) ? A.undo + b : nullptr;
-  if (ud && tid == 0) ud->count = nwin;
-  static_assert(WM <= ZW_MBIG, "ZwUndo holds every window");
-  static_assert(WM % (4 * ZW_THREADS) == 0, "window capacities: four hosts per thread per pass");
-  for (int p0 = 0; p0 < WM && p0 < nwin; p0 += 4 * ZW_THREADS) {
-    double v[4][4];                          // every gather of the pass in flight at once
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int p = p0 + u * ZW_THREADS + tid;
-      const int h = p < nwin ? S.wid[p] : 0;   // (host 0: a valid address, never used)
-#pragma unroll
-      for (int r = 0; r < 4; r++)
-        v[u][r] = p >= nwin ? 0.0 : (pw ? pw->a[r][p] : zw ? zw->a[r][p] : A.avail[(size_t)r * H + h]);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const int p = p0 + u * ZW_THREADS + tid;
-      if (p < nwin) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          wbad |= !(__builtin_fabs(v[u][r]) <= ZW_BIG);
-          S.wa[r][p] = v[u][r];
-        }
-        if (ud) {
-          ud->id[p] = S.wid[p];
-#pragma unroll
-          for (int r = 0; r < 4; r++) ud->a[r][p] = v[u][r];
-        }
-      }
-    }
-  }
-  if (wbad) S.bail = 1;
-  __syncthreads();
-#ifdef PVT_STAMPS
-  const uint64_t t_cap = zstamp();
-#endif
-  if (S.bail || nwin == 0) {
-    if (tid == 0) report(0, KEYED ? 0 : 1);
-    return;
-  }
-  // suffix minima of the chain's demands per 64-task batch: a chunk no host of which fits the
-  // smallest demand still ahead is dead (the walk moves its register chunk past it)
-  const int nsb = min((nt + 63) >> 6, ZW_SB);
-  // (batches before the last were reduced with the certificates above; the last holds the rest)
-  for (int blk = ZW_SB - 1 + wave; blk < nsb; blk += ZW_WAVES) {
-    const int i1 = blk == ZW_SB - 1 ? nt : min(nt, blk * 64 + 64);
-    double bm[4] = {DINF, DINF, DINF, DINF};
-    for (int i = blk * 64 + lane; i < i1; i += 64) {
-      const int w = KEYED ? i : cmap_at(i);
-#pragma unroll
-      for (int r = 0; r < 4; r++) bm[r] = fmin(bm[r], A.dem[(size_t)w * 4 + r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) bm[r] = wave_min_d(bm[r]);
     if (lane == 0) {
 #pragma unroll
-      for (int r = 0; r < 4; r++) S.smin[blk][r] = bm[r];
+      for (int r = 0; r < 4; r++) { S.red[wave][r] = mx[r]; S.red[wave][4 + r] = mn[r]; S.red[wave][8 + r] = ha[r]; }
     }
-  }
-  __syncthreads();
-  static_assert(ZW_SB == 64 && ZW_WAVES == 4, "suffix minima: one wave per dimension, a lane per batch");
-  {                                          // suffix minima: wave r scans dimension r
-    double v = lane < nsb ? S.smin[lane][wave] : DINF;
+    if (bad) S.bail = 1;                        // benign race: every writer stores 1
+    if (um) atomicOr(&S.umask, um);
+    __syncthreads();
+#ifdef PVT_STAMPS
+    t_cert = zstamp();
+#endif
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v = fmin(v, __shfl_down(v, off));
-    if (lane < nsb) S.smin[lane][wave] = v;
+    for (int r = 0; r < 4; r++) {
+      for (int w = 1; w < ZW_WAVES; w++) {
+        mx[r] = fmax(mx[r], S.red[w][r]);
+        mn[r] = fmin(mn[r], S.red[w][4 + r]);
+        ha[r] = FF ? nan_max(ha[r], S.red[w][8 + r]) : fmin(ha[r], S.red[w][8 + r]);
+      }
+      mx[r] = fmax(mx[r], S.red[0][r]);
+      mn[r] = fmin(mn[r], S.red[0][4 + r]);
+      ha[r] = FF ? nan_max(ha[r], S.red[0][8 + r]) : fmin(ha[r], S.red[0][8 + r]);
+    }
+    if (!KEYED && A.cmax && tid < 4) A.cmax[b * 4 + tid] = mx[tid];   // (the validation's fast path)
+    if (!KEYED && A.hcert && tid == 0) {       // the certificate word of the host's verdict
+      int cert = 0;
+      if (!FF) {
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          cert |= ((mx[r] <= 0.0 && mn[r] >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
+      }
+      A.hcert[b] = cert;
+    }
+    bool sep = KEYED;
+    if (FF) {                                  // certificates (2') and (3'): bounded capacities,
+      sep = true;                              // demands >= 0
+#pragma unroll
+      for (int r = 0; r < 4; r++) sep &= (ha[r] <= 0x1p298) && (mn[r] >= 0.0);
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= 0x1p-288);
+    }
+    U = S.umask;
+    if (S.bail || !sep || nt <= 0 || (!KEYED && nt > CHAIN_MAX)) {
+      if (tid == 0) report(0, (KEYED || nt <= 0) ? 0 : 1);
+      return;
+    }
+    const FrontierSlot* pw = A.pwin ? A.pwin + (KEYED ? 0 : b) : nullptr;
+    // the round's first epoch: the window the grouped order's launch prebuilt for the component of
+    // the chain's anchors (its zone set U' covers U; a window over U' is exact, with U' in the
+    // certificates)
+    const ZoneWindow* zw = nullptr;
+    if (!KEYED && WM == ZW_M && !pw && A.zpre && U != 0) {
+      const uint64_t cover = __ballot(zpu != 0 && (U & ~zpu) == 0);
+      if (cover) {
+        const int j = __builtin_ctzll(cover);
+        zw = &A.zpre->w[j];
+        U = (uint32_t)__builtin_amdgcn_readlane((int)zpu, j);
+      }
+    }
+    if (pw) {                                  // host-sharded: the merged window, capacities too
+      const int nw = min(pw->n, ZW_M);
+      for (int p = tid; p < nw; p += ZW_THREADS) {
+        const int32_t h = pw->id[p];
+        S.wid[p] = h;
+        S.wz[p] = KEYED ? 0 : A.zone[h];
+      }
+      if (tid == 0) S.nwin = nw;
+      __syncthreads();
+    } else if (zw) {                           // prebuilt: ids and zones (capacities below)
+      const int nw = min(zw->n, ZW_M);
+      for (int p = tid; p < nw; p += ZW_THREADS) { S.wid[p] = zw->id[p]; S.wz[p] = zw->z[p]; }
+      if (tid == 0) S.nwin = nw;
+      __syncthreads();
+    } else if (KEYED) {                        // window: the zero-key prefix's first hosts
+      const int nw = min(A.kn_dev ? *A.kn_dev : A.kn, ZW_M);
+      for (int p = tid; p < nw; p += ZW_THREADS) { S.wid[p] = A.lo + A.kperm[p]; S.wz[p] = 0; }
+      if (tid == 0) S.nwin = nw;
+      __syncthreads();
+    } else {                                   // window: U's hosts in index order
+      compact_zone_window<WM>(A.zone, Z, U, 0, H, S.wid, S.wz, S.cnt, &S.nwin);
+    }
+    nwin = S.nwin;
+#ifdef PVT_STAMPS
+    t_win = zstamp();
+#endif
+    bool wbad = false;
+    // optimistic apply: the window's hosts and start capacities, saved for an undo (plain stores
+    // nothing waits for)
+    ZwUndo* const ud = (!KEYED && A.undo) ? A.undo + b : nullptr;
+    if (ud && tid == 0) ud->count = nwin;
+    static_assert(WM <= ZW_MBIG, "ZwUndo holds every window");
+    static_assert(WM % (4 * ZW_THREADS) == 0, "window capacities: four hosts per thread per pass");
+    for (int p0 = 0; p0 < WM && p0 < nwin; p0 += 4 * ZW_THREADS) {
+      double v[4][4];                          // every gather of the pass in flight at once
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int p = p0 + u * ZW_THREADS + tid;
+        const int h = p < nwin ? S.wid[p] : 0;   // (host 0: a valid address, never used)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          v[u][r] = p >= nwin ? 0.0 : (pw ? pw->a[r][p] : zw ? zw->a[r][p] : A.avail[(size_t)r * H + h]);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int p = p0 + u * ZW_THREADS + tid;
+        if (p < nwin) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            wbad |= !(__builtin_fabs(v[u][r]) <= ZW_BIG);
+            S.wa[r][p] = v[u][r];
+          }
+          if (ud) {
+            ud->id[p] = S.wid[p];
+#pragma unroll
+            for (int r = 0; r < 4; r++) ud->a[r][p] = v[u][r];
+          }
+        }
+      }
+    }
+    if (wbad) S.bail = 1;
+    __syncthreads();
+#ifdef PVT_STAMPS
+    t_cap = zstamp();
+#endif
+    if (S.bail || nwin == 0) {
+      if (tid == 0) report(0, KEYED ? 0 : 1);
+      return;
+    }
+    // suffix minima of the chain's demands per 64-task batch: a chunk no host of which fits the
+    // smallest demand still ahead is dead (the walk moves its register chunk past it)
+    const int nsb = min((nt + 63) >> 6, ZW_SB);
+    // (batches before the last were reduced with the certificates above; the last holds the rest)
+    for (int blk = ZW_SB - 1 + wave; blk < nsb; blk += ZW_WAVES) {
+      const int i1 = blk == ZW_SB - 1 ? nt : min(nt, blk * 64 + 64);
+      double bm[4] = {DINF, DINF, DINF, DINF};
+      for (int i = blk * 64 + lane; i < i1; i += 64) {
+        const int w = KEYED ? i : cmap_at(i);
+#pragma unroll
+        for (int r = 0; r < 4; r++) bm[r] = fmin(bm[r], A.dem[(size_t)w * 4 + r]);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) bm[r] = wave_min_d(bm[r]);
+      if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) S.smin[blk][r] = bm[r];
+      }
+    }
+    __syncthreads();
+    static_assert(ZW_SB == 64 && ZW_WAVES == 4, "suffix minima: one wave per dimension, a lane per batch");
+    {                                          // suffix minima: wave r scans dimension r
+      double v = lane < nsb ? S.smin[lane][wave] : DINF;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) v = fmin(v, __shfl_down(v, off));
+      if (lane < nsb) S.smin[lane][wave] = v;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   if (wave != 0) return;
 #ifdef PVT_STAMPS
   const uint64_t t_walk = zstamp();
@@ -1262,6 +1418,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     atomicAdd((unsigned long long*)&A.stamps[26], (unsigned long long)st_who);
     atomicAdd((unsigned long long*)&A.stamps[27], (unsigned long long)st_rep);
     atomicAdd((unsigned long long*)&A.stamps[28], (unsigned long long)n_cf);
+    atomicAdd((unsigned long long*)&A.stamps[29], (unsigned long long)(t_load - t_start));
   }
 #endif
 }
@@ -1271,7 +1428,10 @@ void launch_host_min(const double* avail, int H, int lo, int hi, double* part, h
 }
 
 void launch_zwalk(const ZwalkArgs& a, int nchains, hipStream_t st) {
-  PVT_LAUNCH((zwalk_kernel<false, false>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
+  if (a.cert.fast && a.tab.nch > 0 && a.zpre && !a.pwin)
+    PVT_LAUNCH((zwalk_kernel<false, false, false, ZW_M, true>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
+  else
+    PVT_LAUNCH((zwalk_kernel<false, false>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
 }
 void launch_zwalk_big(const ZwalkArgs& a, int nchains, hipStream_t st) {
   PVT_LAUNCH((zwalk_kernel<false, false, false, ZW_MBIG>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);

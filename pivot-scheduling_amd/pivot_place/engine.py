@@ -60,6 +60,7 @@ def load_library(path=None):
         "pvt_zero_walk_stats": ([c_void_p] + [ctypes.POINTER(ctypes.c_int64)] * 3, c_int),
         "pvt_epoch_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
                              ctypes.POINTER(ctypes.c_int64)], c_int),
+        "pvt_prologue_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64)], c_int),
         "pvt_last_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64),
                             ctypes.POINTER(ctypes.c_int64)], c_int),
         "pvt_last_error": ([c_void_p], ctypes.c_char_p),
@@ -811,6 +812,12 @@ class PlacementEngine:
                                                  ctypes.byref(zc)))
         return {"epochs": e.value, "segments": s.value, "rejected": r.value,
                 "frontier_chains": zf.value, "list_chains": zl.value, "longest_chain_tasks": zc.value}
+
+    def prologue_stats(self):
+        """Frontier chains of the last ``place`` that took the walk's fast prologue."""
+        n = ctypes.c_int64()
+        self._check(self.lib.pvt_prologue_stats(self.ctx, ctypes.byref(n)))
+        return {"fast_chains": n.value}
 
     def set_profiling(self, on=True, kernel=None):
         """True / 1: HIP events around every launch; 2: around the named kernels only -- or, with

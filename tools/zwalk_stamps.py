@@ -32,6 +32,13 @@ print("%s H=%d T=%d stats=%s" % (mode, H, T, st))
 print("  prologue   %10.0f cycles per chain" % (buf[0] / nch))
 print("    tables + demand scan %.0f, window ids %.0f, window capacities %.0f, suffix minima %.0f"
       % tuple(buf[20 + k] / nch for k in range(4)))
+# (the first phase again: up to its first barrier -- the entry loads landed and stored to LDS, the
+# position map written; the fast prologue's records too -- and from there to the certificates:
+# the demand scan and reductions, or the fast prologue's reductions and entry scan. With the fast
+# prologue the window phases are 0: its window is part of the entry loads.)
+print("    of the first phase: entry loads + position map %.0f, scan / records + reductions %.0f"
+      % (buf[29] / nch, (buf[20] - buf[29]) / nch))
+print("  fast-prologue chains %d" % eng.prologue_stats()["fast_chains"])
 print("  walk       %10.0f cycles per chain, %.0f per task" % (buf[1] / nch, buf[1] / max(buf[3], 1)))
 print("  chunks     %10.2f per task" % (buf[2] / max(buf[3], 1)))
 print("  tasks      %10d, anchor switches %d" % (buf[3], buf[4]))
