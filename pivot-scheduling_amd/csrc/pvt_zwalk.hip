@@ -78,6 +78,7 @@ constexpr double ZW_BIG = 0x1p500;
 #endif
 constexpr int ZW_UNROLL = PVT_ZW_UNROLL;   // run_bulk pass 1: copies per stop check
 constexpr int ZW_SB = 64;                  // suffix-minimum batches (the last one holds the rest)
+constexpr int32_t ZW_SAME = -1;            // batch log, host entry: the host of the position before
 template <int WM>
 struct ZwalkLDS {
   double wa[4][WM];                        // window capacities (live)
@@ -89,8 +90,8 @@ struct ZwalkLDS {
   double red[ZW_WAVES][12];                // block reductions: max d, min d, min avail
   double smin[ZW_SB][4];                   // suffix minima of the demands, per 64-task batch
   double lg[128][4];                       // the batch's log: capacities after each commit
-  int32_t lgid[128];                       //   and the host (64.. : a run carried into the next batch)
-  int32_t rwho[64], rstart[64];            // run_bulk: host / start flag per run position
+  int32_t lgid[128];                       //   and the host, or ZW_SAME (64.. : a run carried into the next batch)
+  int32_t rwho[64], rstart[64];            // fast prologue: an entry's chain-local range [rstart, rwho)
   uint64_t sbits[CHAIN_MAX / 64];          // chain mode: bit i = a group segment starts at task i
   uint32_t amask[ZMAX];                    // anchor -> its zero-cost zones
   uint32_t umask;
@@ -910,16 +911,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // every copy and the capacities after a lane's last one only: a host's earlier entries in a
     // segment are never final (epoch_final_kernel marks them; validation and apply read the
     // capacities of final entries only, and the keyed / ordered walks read no log).
-    // (each taking lane marks its first run position; a position's host is that of the last
-    // mark at or before it: two LDS round trips, no loop over the taking lanes)
-    S.rstart[lane] = 0;
-    if (asg > 0) { S.rstart[pre] = 1; S.rwho[pre] = cid; }
-    wave_lds_sync();
-    const uint64_t starts = __ballot(S.rstart[lane] != 0);
-    const uint64_t upto = starts & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
-    const int32_t who = upto ? S.rwho[63 - __builtin_clzll(upto)] : 0;
+    // (each taking lane writes its host at its first run position only; the positions after it
+    // keep the batch's "as before" mark, ZW_SAME, and the flush gives each the host of the last
+    // written position at or before it -- once per batch, not once per run)
+    if (asg > 0) S.lgid[k + pre] = cid;
     const int amax = wave_max_i32(asg);
-    if (lane < covered) S.lgid[k + lane] = who;
 #ifdef PVT_STAMPS
     const uint64_t tC = zstamp();
     st_who += tC - tB;
@@ -971,6 +967,36 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   int nanc = A.anc[nw], ncal = A.ord[nw];
   int nw1 = task_at(64 + lane);
   int carry = 0;                             // tasks of this batch a run of the last one placed
+  // The batch's log (WinRec; sup: epoch_final_kernel) goes to HBM at the head of the NEXT batch,
+  // between the copy of that batch's prefetched records and the loads for the one after it (the
+  // last batch's after the loop): the record wait at a batch head then has only operations a
+  // whole batch old before it. Stored right after its batch, behind the loads just issued, the
+  // log's stores were what the next head's vmcnt wait stood on.
+  // Hosts: a single task's winner writes its host at the task's position, a run's taking lanes at
+  // their first positions (run_bulk); every other position of the batch buffer holds ZW_SAME and
+  // takes the host of the last written position at or before it -- the run's taking lanes fill
+  // consecutive ranges in lane order, so that is its host. Positions before the first written one
+  // continue a run carried over the batch end: the host of the last batch's position 63 (fprev).
+  int fk = 0, ftw = 0, fcal = 0;             // the unflushed batch: entries, its tasks' tw / tcal
+  int32_t fprev = 0;
+  S.lgid[lane] = ZW_SAME;
+  S.lgid[64 + lane] = ZW_SAME;
+  auto flush_log = [&]() {
+    if (UNI(fk > 0)) {
+      const int32_t raw = S.lgid[lane];
+      const uint64_t upto = __ballot(raw != ZW_SAME) & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
+      const int32_t from = __shfl(raw, upto ? 63 - __builtin_clzll(upto) : 0);
+      const int32_t id = upto ? from : fprev;
+      fprev = __builtin_amdgcn_readlane(id, 63);
+      if (lane < fk) {
+        WinRec& e = A.wlog[ftw];
+        e.s = 0.0;
+        e.id = id;
+        e.a[0] = S.lg[lane][0]; e.a[1] = S.lg[lane][1]; e.a[2] = S.lg[lane][2]; e.a[3] = S.lg[lane][3];
+        A.placement[fcal] = id;
+      }
+    }
+  };
   for (int i0 = 0; UNI(i0 < nt && !failed); i0 += 64) {
 #ifdef PVT_STAMPS
     uint64_t tb0 = zstamp();
@@ -981,6 +1007,12 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     const double td[4] = {nd0, nd1, nd2, nd3};
     const int tanc = nanc;
     const int tcal = ncal;
+    // (the record wait, explicit and ahead of the stores: left to the compiler it lands at the
+    // records' first use, behind the flush, and waits for the stores just issued)
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0)
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);
+    flush_log();                             // (before the carry shuffle below moves lg[64..])
     if (i0 + 64 < nt) {                      // (uniform) batch b + 1's records, b + 2's positions
       nw = nw1;
       nd0 = A.dem[(size_t)nw * 4 + 0]; nd1 = A.dem[(size_t)nw * 4 + 1];
@@ -1112,13 +1144,15 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     st_batch += zstamp() - tb0;
 #endif
     int k = carry;
-    if (carry) {                             // the carried run's log entries to their positions
-      wave_lds_sync();
+    {                                        // the carried run's log entries to their positions;
+      wave_lds_sync();                       // every other host entry back to "as before"
+      const int32_t cid = lane < carry ? S.lgid[64 + lane] : ZW_SAME;
       if (lane < carry) {
 #pragma unroll
         for (int r = 0; r < 4; r++) S.lg[lane][r] = S.lg[64 + lane][r];
-        S.lgid[lane] = S.lgid[64 + lane];
       }
+      S.lgid[lane] = cid;
+      S.lgid[64 + lane] = ZW_SAME;
       wave_lds_sync();
     }
     while (UNI(k < kn)) {
@@ -1347,19 +1381,15 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #ifdef PVT_STAMPS
     tb0 = zstamp();
 #endif
-    if (lane < k) {                          // the batch's log (WinRec; sup: epoch_final_kernel)
-      WinRec& e = A.wlog[tw];
-      const int32_t id = S.lgid[lane];
-      e.s = 0.0;
-      e.id = id;
-      e.a[0] = S.lg[lane][0]; e.a[1] = S.lg[lane][1]; e.a[2] = S.lg[lane][2]; e.a[3] = S.lg[lane][3];
-      A.placement[tcal] = id;
-    }
+    fk = __builtin_amdgcn_readfirstlane(k);
+    ftw = tw;
+    fcal = tcal;
     carry = __builtin_amdgcn_readfirstlane(k > kn ? k - kn : 0);
 #ifdef PVT_STAMPS
     st_batch += zstamp() - tb0;
 #endif
   }
+  flush_log();                               // the last batch walked
   if (KEYED) {   // the window's capacities to global availability: the keyed path goes on there
     store_chunk(p0);
     store_b();
