@@ -226,6 +226,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   uint64_t st_search = 0, st_p1 = 0, st_p2 = 0, n_probe = 0, n_iter = 0, st_batch = 0, n_single = 0;
   uint64_t st_setup = 0, st_loop = 0, st_who = 0, st_rep = 0;   // run_bulk's parts
   uint64_t n_cf = 0;                                              // runs counted in closed form
+  uint64_t n_part = 0, s_pasg = 0, n_fromc = 0, n_rep = 0;       // pass 2: calls with a partial lane, its asg; replays from c; copies
 #endif
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // chain tables: by value in the arguments (A.tab; the host sends them only for chains of at
@@ -805,9 +806,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   // lane subtracts d again and again in parallel (cnt = copies taken; the active set only
   // shrinks), until the lanes up to the lowest active one u have taken R copies (fb = copies of
   // the finished lanes below u, u itself has taken t) or no lane takes another. Lane l then takes
-  // asg = clamp(R - (copies of the lanes before it), 0, cnt) tasks; pass 2 replays exactly those
-  // subtractions on the chunk's registers, logging the capacities after each commit at the
-  // task's batch position. Returns the tasks placed (>= 1; fewer than R when the chunk runs
+  // asg = clamp(R - (copies of the lanes before it), 0, cnt) tasks; pass 2 leaves the chunk's
+  // registers at the capacities after exactly those subtractions (from pass 1's snapshot of the
+  // lane plus at most a block's copies, or replayed from the start) and logs them at the batch
+  // position of the lane's last task. Returns the tasks placed (>= 1; fewer than R when the chunk runs
   // out). Bit-exact: the same sequential subtractions as one task after the other.
   // (CFT: IntC<1> where the closed-form counts are compiled in -- the hot loop's call only: a
   // copy at each of the four call sites ran the walk out of scalar registers)
@@ -829,6 +831,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     st_setup += tA1 - tA;
 #endif
     bool cf = false;                         // the closed-form counts are certified
+    double s0 = c0, s1 = c1, s2 = c2, s3 = c3;   // pass 1's snapshots (below; c until a block start takes one)
+    int t = 0;                               // copies pass 1 has subtracted (0: it did not run)
 #if PVT_ZW_CF
     if (decltype(cft)::value && R >= 2) {
       // Pass 1 in closed form (copies_cf): every lane of m0 counts its copies from a quotient,
@@ -855,36 +859,67 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #endif
     if (!cf) {
       // Pass 1: without per-lane masks: with d >= 0 a lane that fails a copy fails every later
-      // one (its residual only falls further), so every lane just keeps subtracting, recording
-      // the last copy that fit (= the copies it takes); lanes outside m0 start at -inf.
+      // one (its residual only falls further), so every lane just keeps subtracting, counting
+      // the copies that fit (= the copies it takes); lanes outside m0 start at -inf.
       // ZW_UNROLL copies per check (a check past the stop only raises counts of lanes that get no
       // task or no more tasks: asg clamps them).
+      // The loop is bound by issue, not by latency (tools/f64_chain.hip: a dependent v_add_f64
+      // link is 9 cycles, an instruction of a lone wave issues every ~5), so a copy costs its
+      // instructions: the subtractions, the minima, one compare and one carry add -- a copy that
+      // fits adds one to cnt (exact: a lane that fails a copy fails every later one, so its
+      // count is the number of copies that fit). The copies of a block are software-pipelined in
+      // the source (subtractions of copy j, pair minima of j - 1, last minimum of j - 2, test of
+      // j - 3) and pinned by scheduling barriers, so that no instruction waits for the one
+      // before it. Left alone the compiler puts each minimum and compare right behind what it
+      // reads.
+      // Snapshots for pass 2: s = the capacities at the last block start at which the lane still
+      // fit every copy so far (two selects per changing dimension per block, not per copy).
       double x0 = on1 ? c0 : -DINF, x1 = on1 ? c1 : -DINF, x2 = on1 ? c2 : -DINF, x3 = on1 ? c3 : -DINF;
-      int t = 0;
       auto pass1 = [&](auto dims) {
         constexpr int D = decltype(dims)::value;
+        constexpr int U = ZW_UNROLL;
         int u = __builtin_ctzll(m0), fb = 0;
+        bool f = false;
         for (;;) {
           t = __builtin_amdgcn_readfirstlane(t);
           u = __builtin_amdgcn_readfirstlane(u);
           fb = __builtin_amdgcn_readfirstlane(fb);
-          bool f = false;
-#pragma unroll
-          for (int j = 1; j <= ZW_UNROLL; j++) {
-            x0 -= d0; x1 -= d1;
-            if (D == 4) { x2 -= d2; x3 -= d3; }
-            f = fit_res<STRICT>(D == 4 ? fmin(fmin(x0, x1), fmin(x2, x3)) : fmin(x0, x1));
-            cnt = f ? t + j : cnt;
+          if (t > 0) {                           // (f: the lane took the last block's last copy)
+            s0 = f ? x0 : s0; s1 = f ? x1 : s1;
+            if (D == 4) { s2 = f ? x2 : s2; s3 = f ? x3 : s3; }
           }
+          double a0[U], a1[U], a2[U], a3[U], mp[U], mq[U], mm[U];
+#pragma unroll
+          for (int j = 0; j < U + 3; j++) {
+            if (j < U) {
+              a0[j] = (j ? a0[j - 1] : x0) - d0;
+              a1[j] = (j ? a1[j - 1] : x1) - d1;
+              if (D == 4) { a2[j] = (j ? a2[j - 1] : x2) - d2; a3[j] = (j ? a3[j - 1] : x3) - d3; }
+            }
+            if (j >= 1 && j - 1 < U) {
+              mp[j - 1] = fmin(a0[j - 1], a1[j - 1]);
+              if (D == 4) mq[j - 1] = fmin(a2[j - 1], a3[j - 1]);
+            }
+            if (j >= 2 && j - 2 < U) mm[j - 2] = D == 4 ? fmin(mp[j - 2], mq[j - 2]) : mp[j - 2];
+            if (j >= 3) {
+              f = fit_res<STRICT>(mm[j - 3]);
+              cnt += f ? 1 : 0;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          x0 = a0[U - 1]; x1 = a1[U - 1];
+          if (D == 4) { x2 = a2[U - 1]; x3 = a3[U - 1]; }
           t += ZW_UNROLL;
-          const uint64_t an = __ballot(f);       // lanes that took copy t
-          if (UNI(an == 0)) break;
+          // (the stop tests on scalars: a ballot through rfl_u64, t / u / fb / R through
+          // readfirstlane -- plain scalar compares, no round trip through a vector register)
+          const uint64_t an = rfl_u64(__ballot(f));   // lanes that took copy t
+          if (an == 0) break;
           const int un = __builtin_ctzll(an);
           if (un != u) {                         // (u only rises: every lane below un is done)
             u = un;
             fb = __builtin_amdgcn_readlane(wave_incl_scan_dpp(cnt), u - 1);
           }
-          if (UNI(fb + t >= R)) break;
+          if (fb + t >= R) break;
         }
       };
       if (two) pass1(IntC<2>{});
@@ -904,10 +939,16 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     const uint64_t tB = zstamp();
     st_p1 += tB - tA;
 #endif
-    // Pass 2: the lanes that take tasks (few: a host takes many copies) in a scalar loop --
-    // each lane of the run's batch positions learns its host -- and every such lane replays
-    // exactly its own subtractions (the same sequential subtractions as task after task, so
-    // bit-exact), predicated in steps of four up to the largest count. The log keeps the host of
+    // Pass 2: a taking lane marks its host and ends at its capacities after asg copies: the same
+    // sequential subtractions as task after task, so bit-exact. Pass 1 held most of them: the
+    // snapshot s is the lane's value after sbc copies, sbc = the last block start it was still
+    // whole at (the largest multiple of ZW_UNROLL up to cnt, at most the last block's start).
+    // A lane with asg >= sbc -- every lane that takes all its copies, and the last taking lane
+    // when the run ends in the block that stopped pass 1 -- goes on from s with asg - sbc copies,
+    // at most a block's (x - d by v_add_f64 and fma(-1, d, x) round once to the same value);
+    // a lane that takes fewer copies than its snapshot holds (at most one per call: the last
+    // taking lane) replays its asg copies from c. A lane that takes nothing has sbc > 0 = asg or
+    // s == c: it keeps c. The log keeps the host of
     // every copy and the capacities after a lane's last one only: a host's earlier entries in a
     // segment are never final (epoch_final_kernel marks them; validation and apply read the
     // capacities of final entries only, and the keyed / ordered walks read no log).
@@ -915,32 +956,67 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // keep the batch's "as before" mark, ZW_SAME, and the flush gives each the host of the last
     // written position at or before it -- once per batch, not once per run)
     if (asg > 0) S.lgid[k + pre] = cid;
-    const int amax = wave_max_i32(asg);
+    const int sbc = min(cnt / ZW_UNROLL * ZW_UNROLL, max(t - ZW_UNROLL, 0));
+#ifdef PVT_ZW_REPLAY_FULL
+    const bool snap = false;                 // A/B: every lane replays its asg copies from c
+#else
+    const bool snap = asg >= sbc;
+#endif
+    const int nrep = snap ? asg - sbc : asg;
+    c0 = snap ? s0 : c0; c1 = snap ? s1 : c1;
+    c2 = snap ? s2 : c2; c3 = snap ? s3 : c3;  // (two: s2 == c2, s3 == c3)
+    // the copies left, a scalar: at most a block's from a snapshot (4 or 8: one ballot), and the
+    // count of the one lane that starts over, if any
+    const uint64_t over = rfl_u64(__ballot(asg > 0 && !snap));
+#ifdef PVT_ZW_REPLAY_FULL
+    (void)over;
+    const int nmax = wave_max_i32(asg);      // (every taking lane starts over)
+#else
+    int nmax = rfl_u64(__ballot(snap && nrep > 4)) ? ZW_UNROLL : rfl_u64(__ballot(snap && nrep > 0)) ? 4 : 0;
+    if (over) nmax = max(nmax, __builtin_amdgcn_readlane(asg, __builtin_ctzll(over)));
+#if PVT_ZW_CF
+    // (closed-form counts: pass 1 did not run, so s == c, sbc == 0 and every taking lane replays
+    // all its asg copies, which no block bounds)
+    if (cf) nmax = wave_max_i32(asg);
+#endif
+#endif
 #ifdef PVT_STAMPS
+    {
+      const uint64_t part = __ballot(asg > 0 && asg < cnt);
+      n_part += part != 0;
+      if (part) s_pasg += (uint64_t)__builtin_amdgcn_readlane(asg, __builtin_ctzll(part));
+      n_fromc += over != 0;
+    }
     const uint64_t tC = zstamp();
     st_who += tC - tB;
 #endif
     // (c - d as fma(-1, d, c), rounded once, the same bits; fma(-0, d, c) == c for the finite d
     // and c of a proven chain: one 0/1 factor per copy for every dimension)
     if (two) {
-      for (int m = 0; m < amax; m += 4) {
+      for (int m = 0; m < nmax; m += 4) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-          const double o = m + u < asg ? -1.0 : -0.0;
+          const double o = m + u < nrep ? -1.0 : -0.0;
           c0 = __builtin_fma(o, d0, c0);
           c1 = __builtin_fma(o, d1, c1);
         }
+#ifdef PVT_STAMPS
+        n_rep += 4;
+#endif
       }
     } else {
-      for (int m = 0; m < amax; m += 4) {
+      for (int m = 0; m < nmax; m += 4) {
 #pragma unroll
         for (int u = 0; u < 4; u++) {
-          const double o = m + u < asg ? -1.0 : -0.0;
+          const double o = m + u < nrep ? -1.0 : -0.0;
           c0 = __builtin_fma(o, d0, c0);
           c1 = __builtin_fma(o, d1, c1);
           c2 = __builtin_fma(o, d2, c2);
           c3 = __builtin_fma(o, d3, c3);
         }
+#ifdef PVT_STAMPS
+        n_rep += 4;
+#endif
       }
     }
 #ifdef PVT_STAMPS
@@ -1439,6 +1515,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     atomicAdd((unsigned long long*)&A.stamps[11], (unsigned long long)n_iter);
     atomicAdd((unsigned long long*)&A.stamps[12], (unsigned long long)st_batch);
     atomicAdd((unsigned long long*)&A.stamps[13], (unsigned long long)n_single);
+    atomicAdd((unsigned long long*)&A.stamps[14], (unsigned long long)n_part);
+    atomicAdd((unsigned long long*)&A.stamps[15], (unsigned long long)s_pasg);
+    atomicAdd((unsigned long long*)&A.stamps[30], (unsigned long long)n_fromc);
+    atomicAdd((unsigned long long*)&A.stamps[31], (unsigned long long)n_rep);
     atomicAdd((unsigned long long*)&A.stamps[20], (unsigned long long)(t_cert - t_start));
     atomicAdd((unsigned long long*)&A.stamps[21], (unsigned long long)(t_win - t_cert));
     atomicAdd((unsigned long long*)&A.stamps[22], (unsigned long long)(t_cap - t_win));

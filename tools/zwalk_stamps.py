@@ -48,6 +48,17 @@ print("  pass 1     %10.0f cycles per bulk call, %.1f iterations" % (buf[8] / ma
 print("  pass 2     %10.0f cycles per bulk call" % (buf[9] / max(buf[6], 1)))
 print("    per run: setup %.0f, pass-1 loop %.0f, who loop + host ids %.0f, replay %.0f"
       % tuple(buf[24 + k] / max(buf[6], 1) for k in range(4)))
+# (blocks: of ZW_UNROLL = 8 copies, the default; a variant built with another -DPVT_ZW_UNROLL reads
+# wrong here. Pass 1 in copies: the loop's cycles over the copies it subtracted, block ends included; pass 2:
+# "who loop + host ids" holds the host mark and the choice between snapshot and start, "replay" the
+# copies after it -- a partial lane, 0 < asg < cnt, is the run's last taking lane; it replays from
+# the start only where its asg lies below its snapshot)
+print("    pass-1 loop: %.1f cycles per copy (%.1f copies in %.2f blocks per call)"
+      % (buf[25] / max(buf[11], 1), buf[11] / max(buf[6], 1), buf[11] / 8 / max(buf[6], 1)))
+print("    pass 2: snapshot choice + host ids %.0f, replay %.0f cycles per call for %.1f copies (%.1f cycles per copy)"
+      % (buf[26] / max(buf[6], 1), buf[27] / max(buf[6], 1), buf[31] / max(buf[6], 1), buf[27] / max(buf[31], 1)))
+print("    calls with a partial lane: %d of %d, mean asg %.1f; calls that replayed a lane from the start: %d"
+      % (buf[14], buf[6], buf[15] / max(buf[14], 1), buf[30]))
 print("    runs counted in closed form: %d of %d" % (buf[28], buf[6]))
 print("  batches    %10.0f cycles per task (records, run masks, log flush)" % (buf[12] / max(buf[3], 1)))
 print("  single     %10d tasks on the one-task hot path" % buf[13])
