@@ -160,6 +160,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
   if (const char* e = getenv("PVT_CHAIN_TAB")) ctx->t_chain_tab = atoi(e) != 0;        // A/B
   if (const char* e = getenv("PVT_EPOCH_TAIL")) ctx->t_epoch_tail = atoi(e) != 0;      // A/B
   if (const char* e = getenv("PVT_CHAIN_CERT")) ctx->t_chain_cert = atoi(e) != 0;      // A/B
+  if (const char* e = getenv("PVT_ZW_RUNREM")) ctx->t_zw_runrem = atoi(e) != 0;        // A/B
   if (const char* e = getenv("PVT_MERGE_SMALL")) ctx->t_merge_bitonic = atoi(e) == 0;  // A/B
   if (const char* e = getenv("PVT_RES_WAVES")) ctx->res_waves = atoi(e) == 8 ? 8 : atoi(e) == 2 ? 2 : atoi(e) == 1 ? 1 : 4;  // A/B
   *out = ctx;
@@ -180,7 +181,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->ksorttmp, &ctx->kflag, &ctx->ep_dev, &ctx->wres, &ctx->hmin, &ctx->cmax, &ctx->fwin,
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
-                 &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
+                 &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
                  &ctx->chk_owner};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
@@ -317,8 +318,9 @@ extern "C" int pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills) 
 extern "C" int pvt_debug_commit_stamps(pvt_ctx* ctx, uint64_t* out, int n) {
   if (!ctx || !out || n < 8) return PVT_EINVAL;
 #ifdef PVT_STAMPS
-  // 32 counters, then per-round cycles of the resident kernel (4096 rounds)
-  constexpr int NW = 32 + 4096;
+  // 32 counters, then per-round cycles of the resident kernel (4096 rounds), then the frontier
+  // walk's per-chain words
+  constexpr int NW = ZW_STAMP_CHAIN + 8 * ZW_STAMP_CHAINS;
   if (!ctx->stamps) {
     if (hipMalloc((void**)&ctx->stamps, sizeof(uint64_t) * NW) != hipSuccess) return PVT_ENOMEM;
     (void)hipMemset(ctx->stamps, 0, sizeof(uint64_t) * NW);

@@ -128,6 +128,7 @@ struct RoundState {
   bool hmin_pre = false;          // the first epoch's host minima were queued by round_begin
   bool zpre = false;              // ... and its zero-cost windows were prebuilt (ctx->zwin)
   bool gcert = false;             // ... and the groups' certificates were written (ctx->gcert)
+  bool runrem = false;            // ... and the gathered tasks' run lengths (ctx->run_rem)
   bool stage_flag = false;        // the grouped order's counts are signalled by ctx->flag_host
   bool gathered = false;          // ... and group_sort_gather_kernel wrote the gathered order
   bool prep_fused = false;        // build_order's order_scatter_kernel filled placement / zone tables
@@ -194,6 +195,7 @@ struct pvt_ctx {
   int t_chain_tab = 1;            // PVT_CHAIN_TAB: 0 = chain tables uploaded before the walk
   int t_epoch_tail = 1;           // PVT_EPOCH_TAIL: 0 = every frontier-walked epoch runs the tail kernels
   int t_chain_cert = 1;           // PVT_CHAIN_CERT: 0 = every frontier walk scans its chain's demand rows
+  int t_zw_runrem = 1;            // PVT_ZW_RUNREM: 0 = the walk finds its runs itself, 64 tasks at the most
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
   int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
   int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
@@ -208,6 +210,7 @@ struct pvt_ctx {
   Buf zwin;                       // the first epoch's zero-cost windows (ZoneWindows)
   Buf zundo;                      // frontier walks' optimistic apply: per chain, what undoes it (ZwUndo)
   Buf gcert;                      // the grouped order's group certificates (GroupCert per group)
+  Buf run_rem;                    //   and its run lengths (GatherOut.run_rem, int32 per gathered task)
   int32_t* ep_host = nullptr;     // pinned staging of ep_dev
   int32_t* ep_hdev = nullptr;     // ep_host's device address (the accept kernel's readback)
   pvt_round* rstage = nullptr;    // pvt_place_batch: descriptors staged for the device (pinned)

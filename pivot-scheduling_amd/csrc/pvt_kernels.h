@@ -321,6 +321,10 @@ struct ZwalkArgs {
   const double* dem;      // window tasks [nt][4]
   const int32_t* anc;     // window tasks' anchors
   const int32_t* ord;     // window task -> caller index (placement)
+  // window tasks' run lengths (GatherOut.run_rem), or NULL: the fast prologue's instance takes a
+  // run's length from it, min(run_rem, ZW_RMAX), instead of comparing the batch's demand rows;
+  // set only where the order came from this round's grouped-order launch (chain_cert)
+  const int32_t* run_rem;
   const double* csum;
   const double* bsum;
   const int32_t* coff;
@@ -363,6 +367,11 @@ struct ZwalkArgs {
   ChainCert cert;         // chain mode: cert.fast = the fast prologue (launch_zwalk), or none
 };
 constexpr int ZW_CERT_FAST = 1 << 8;
+// PVT_STAMPS builds: chain b's own words in the stamps buffer, 8 from ZW_STAMP_CHAIN + 8 b (past
+// the 32 counters and the resident kernel's 4096 rounds): run_bulk calls, continued-run calls,
+// cycles between calls, cycles of the continued calls with the gap before each, walk cycles,
+// tasks walked, chain tasks
+constexpr int ZW_STAMP_CHAIN = 32 + 4096, ZW_STAMP_CHAINS = 64;
 constexpr int ZW_MIN_PARTS = 256;
 // per-dimension minima of avail over hosts [lo, hi) into part[ZW_MIN_PARTS][4]
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);
@@ -690,6 +699,9 @@ struct GatherOut {
   const int32_t* zone;        // zwin != NULL: Z more blocks prebuild the first epoch's zero-cost
   struct ZoneWindows* zwin;   //   windows from the snapshot (ZoneWindows), or NULL
   struct GroupCert* gcert;    // [G] group certificates written by the groups' blocks, or NULL
+  // [T] gathered order, with gcert only, or NULL: the tasks from p to the end of p's stretch of
+  // bit-identical demand rows inside its group, p counted (the frontier walk's run lengths)
+  int32_t* run_rem;
 };
 static_assert(GC_SUB * 64 == GSORT_MAX, "a group record holds every sub-batch of a sorted group");
 void launch_group_sort_gather(const PrepArgs& a, const GatherOut& o, hipStream_t st);

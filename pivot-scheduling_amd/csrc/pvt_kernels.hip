@@ -1577,18 +1577,38 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   double gmx[4] = {-DINF, -DINF, -DINF, -DINF}, gmn[4] = {DINF, DINF, DINF, DINF};
   bool gbad = false;
+  // Run lengths (GatherOut.run_rem): a task starts a stretch when its row differs, in bits, from
+  // the sorted row before it (the lane below's; a wave's lane 0 loads that row itself, with its
+  // own, so no load waits for another). The start flags go by ballot into a bit table in k past
+  // the reduction's words; after the certificate's barrier each task looks up the next start.
+  uint64_t* const sbt = (gc && O.run_rem) ? k + 256 : nullptr;
+  static_assert(GSORT_MAX / 64 + 256 <= GSORT_MAX && 16 * 8 <= 256, "start bits beside the reduction");
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + tid;
-    double d[4] = {0.0, 0.0, 0.0, 0.0};
+    double d[4] = {0.0, 0.0, 0.0, 0.0}, pd[4] = {0.0, 0.0, 0.0, 0.0};
     if (i < n) {
       const int p = a + i, t = v[i];
       O.ord[p] = t;
       if (O.order_out) O.order_out[p] = t;
       double* o = O.dem_ord + (size_t)p * 4;
       d[0] = A.dem[t]; d[1] = A.dem[(size_t)T + t]; d[2] = A.dem[2 * (size_t)T + t]; d[3] = A.dem[3 * (size_t)T + t];
+      if (sbt && lane == 0 && i > 0) {
+        const int tp = v[i - 1];
+        pd[0] = A.dem[tp]; pd[1] = A.dem[(size_t)T + tp]; pd[2] = A.dem[2 * (size_t)T + tp]; pd[3] = A.dem[3 * (size_t)T + tp];
+      }
       o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; o[3] = d[3];
       O.anc_ord[p] = anc;
       O.grp_ord[p] = g;
+    }
+    if (sbt && i0 + wave * 64 < n) {          // (uniform; lanes past n count as starts: a stretch ends at n)
+      bool start = i >= n || i == 0;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const double up = __shfl_up(d[r], 1);
+        start |= __double_as_longlong(lane == 0 ? pd[r] : up) != __double_as_longlong(d[r]);
+      }
+      const uint64_t sm = __ballot(start);
+      if (lane == 0) sbt[(i0 >> 6) + wave] = sm;
     }
     if (gc && i0 + wave * 64 < n) {           // (uniform: the wave holds a sub-batch)
 #pragma unroll
@@ -1620,6 +1640,17 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
       if (tid < 4) gc->mx[tid] = x; else gc->mn[tid - 4] = x;
     }
     if (tid == 0) { gc->bad = gbad ? 1 : 0; gc->n = n; }
+    if (sbt) {                                // (the barrier above: every wave's start bits are in)
+      const int nw = (n + 63) >> 6;
+      for (int i = tid; i < n; i += 1024) {
+        int w = (i + 1) >> 6;
+        uint64_t m = w < nw ? sbt[w] >> ((i + 1) & 63) : 0ull;
+        int nx = i + 1;                       // the next start at or after i + 1 (n: none)
+        while (m == 0 && ++w < nw) { m = sbt[w]; nx = w * 64; }
+        nx = m ? nx + __builtin_ctzll(m) : n;
+        O.run_rem[a + i] = min(nx, n) - i;
+      }
+    }
   }
 #ifdef PVT_STAMPS
   __syncthreads();

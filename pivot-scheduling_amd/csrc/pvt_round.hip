@@ -99,6 +99,7 @@ static int build_order(pvt_ctx* ctx, const pvt_round* r, int32_t** ord_out, bool
   R.ginfo = false;
   R.zpre = false;
   R.gcert = false;
+  R.runrem = false;
   if (grouped && r->n_groups <= (1 << 20)) {
     // one synchronisation: group counts, group anchors and the cost table to the host
     const int G = r->n_groups;
@@ -153,14 +154,18 @@ static int build_order(pvt_ctx* ctx, const pvt_round* r, int32_t** ord_out, bool
         // (the groups' certificates for the first epoch's frontier walk, with its windows)
         const bool gc = zw && ctx->t_chain_cert;
         if (gc) ENSURE(ctx->gcert, sizeof(GroupCert) * (size_t)GCOMPACT_MAX);
+        const bool rr = gc && ctx->t_zw_runrem;   // (run lengths for that walk, from the same rows)
+        if (rr) ENSURE(ctx->run_rem, sizeof(int32_t) * (size_t)T);
         launch_group_sort_gather(pa, GatherOut{cur, P<double>(ctx->dem_ord), P<int32_t>(ctx->anc_ord),
                                                P<int32_t>(ctx->grp_ord), r->order, r->avail,
                                                r->n_hosts, hmin, ctx->stamps, r->zone,
                                                zw ? zwin : nullptr,
-                                               gc ? P<GroupCert>(ctx->gcert) : nullptr}, st);
+                                               gc ? P<GroupCert>(ctx->gcert) : nullptr,
+                                               rr ? P<int32_t>(ctx->run_rem) : nullptr}, st);
         if (hmin_done) *hmin_done = hmin != nullptr;
         R.zpre = zw;
         R.gcert = gc;
+        R.runrem = rr;
         R.gathered = true;
         R.ginfo = ca;
         *pending = true;
@@ -462,6 +467,7 @@ int pvt::round_begin(pvt_ctx* ctx, const pvt_round* rin, int lo, int hi, int wor
     if ((rc = build_order_check(ctx, r, &redo))) return rc;
     if (redo) {
       R.gcert = false;                        // (a group had no record)
+      R.runrem = false;
       if ((rc = build_order_radix(ctx, r, &R.ord))) return rc;
       if ((rc = order_out())) return rc;
     }

@@ -487,8 +487,12 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       // the fast prologue: the groups' certificates instead of a pass over the chains' rows
       UndoWin uw{};
       const bool fastp = tabv && za.zpre && chain_cert(ctx, t0, E, za.cert, uw);
+      // (run lengths: with the fast prologue only -- every segment a whole group of this round's
+      // grouped-order launch, the epoch from task 0, so gathered position = epoch task)
+      if (fastp && R.runrem && ctx->t_zw_runrem) za.run_rem = P<int32_t>(ctx->run_rem);
       R.zpre = false;
       R.gcert = false;
+      R.runrem = false;
       ea.cmax = P<double>(ctx->cmax);
       ea.coff = dev + EP_COFF;
       ea.nch = nch;

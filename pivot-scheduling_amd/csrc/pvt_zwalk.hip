@@ -79,6 +79,19 @@ constexpr double ZW_BIG = 0x1p500;
 constexpr int ZW_UNROLL = PVT_ZW_UNROLL;   // run_bulk pass 1: copies per stop check
 constexpr int ZW_SB = 64;                  // suffix-minimum batches (the last one holds the rest)
 constexpr int32_t ZW_SAME = -1;            // batch log, host entry: the host of the position before
+#ifndef PVT_ZW_RMAX
+#define PVT_ZW_RMAX 192
+#endif
+#ifndef PVT_ZW_RMIN
+// the hot loop places a run through run_bulk from this many tasks on (2, 4 and 8 measured against
+// each other: EXPERIMENTS.md, round 11)
+#define PVT_ZW_RMIN 2
+#endif
+constexpr int ZW_RMAX = PVT_ZW_RMAX;       // tasks one run_bulk call places at the most (run lengths from the order launch)
+constexpr int ZW_RMIN = PVT_ZW_RMIN;
+constexpr int ZW_LOGN = 256;               // positions of the batch log's ring
+static_assert((ZW_LOGN & (ZW_LOGN - 1)) == 0 && ZW_LOGN >= 64 + ZW_RMAX && ZW_RMAX >= 64 && ZW_RMIN >= 2,
+              "a run from the current batch writes at most 64 + ZW_RMAX positions past the oldest unflushed one");
 template <int WM>
 struct ZwalkLDS {
   double wa[4][WM];                        // window capacities (live)
@@ -89,8 +102,8 @@ struct ZwalkLDS {
   int32_t cnt[ZW_SCAN][ZW_WAVES];          // window build: hits per (pass row, wave)
   double red[ZW_WAVES][12];                // block reductions: max d, min d, min avail
   double smin[ZW_SB][4];                   // suffix minima of the demands, per 64-task batch
-  double lg[128][4];                       // the batch's log: capacities after each commit
-  int32_t lgid[128];                       //   and the host, or ZW_SAME (64.. : a run carried into the next batch)
+  double lg[ZW_LOGN][4];                   // the log's ring, by chain position & (ZW_LOGN - 1): capacities after each commit
+  int32_t lgid[ZW_LOGN];                   //   and the host, or ZW_SAME (a run writes ahead of its batch)
   int32_t rwho[64], rstart[64];            // fast prologue: an entry's chain-local range [rstart, rwho)
   uint64_t sbits[CHAIN_MAX / 64];          // chain mode: bit i = a group segment starts at task i
   uint32_t amask[ZMAX];                    // anchor -> its zero-cost zones
@@ -146,7 +159,7 @@ template <int N> struct IntC { static constexpr int value = N; };
 //    below |x| + j d): e_k and e_{k+1} must clear twice that bound on their side of 0.
 // Anything else is "unsure" and the caller subtracts copy by copy. (x >= d > 0 here: the lane
 // fits one copy; counts are capped at ZW_CAP, more than any run takes.)
-constexpr int ZW_CAP = 128;
+constexpr int ZW_CAP = 256;
 __device__ __forceinline__ int lowbit_exp(double v) {   // exponent of v's lowest set bit (0: big)
   const uint64_t b = (uint64_t)__double_as_longlong(v);
   const uint64_t m = b & ((1ull << 52) - 1);
@@ -227,6 +240,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   uint64_t st_setup = 0, st_loop = 0, st_who = 0, st_rep = 0;   // run_bulk's parts
   uint64_t n_cf = 0;                                              // runs counted in closed form
   uint64_t n_part = 0, s_pasg = 0, n_fromc = 0, n_rep = 0;       // pass 2: calls with a partial lane, its asg; replays from c; copies
+  // per chain (ZW_STAMP_CHAIN): run_bulk calls; those that continue a run a cap cut (the task
+  // before the call's first has its demand row, anchor and segment: Ec, per batch); the cycles
+  // between one call's return and the next one's entry; a continued call's cost from the return
+  // before it to its own
+  uint64_t n_calls = 0, n_cont = 0, st_between = 0, st_cont = 0, t_ret = 0, Ec = 0;
 #endif
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // chain tables: by value in the arguments (A.tab; the host sends them only for chains of at
@@ -817,6 +835,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
                       double d1, double d2, double d3, uint64_t m0, int R, int k) -> int {
 #ifdef PVT_STAMPS
     const uint64_t tA = zstamp();
+    const uint64_t gap = t_ret ? tA - t_ret : 0;
+    const bool contd = (Ec >> (k & 63)) & 1ull;
+    n_calls++;
+    st_between += gap;
 #endif
     // (Dimensions of demand +0 keep their capacity, x - +0 == x bit for bit, and fit as they did
     // for m0: with d2 = d3 = +0, the trace's disk and gpus, only cpus and memory are counted and
@@ -955,7 +977,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // (each taking lane writes its host at its first run position only; the positions after it
     // keep the batch's "as before" mark, ZW_SAME, and the flush gives each the host of the last
     // written position at or before it -- once per batch, not once per run)
-    if (asg > 0) S.lgid[k + pre] = cid;
+    if (asg > 0) S.lgid[(k + pre) & (ZW_LOGN - 1)] = cid;
     const int sbc = min(cnt / ZW_UNROLL * ZW_UNROLL, max(t - ZW_UNROLL, 0));
 #ifdef PVT_ZW_REPLAY_FULL
     const bool snap = false;                 // A/B: every lane replays its asg copies from c
@@ -1023,11 +1045,13 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     st_rep += zstamp() - tC;
 #endif
     if (asg > 0) {
-      const int q = k + pre + asg - 1;
+      const int q = (k + pre + asg - 1) & (ZW_LOGN - 1);
       S.lg[q][0] = c0; S.lg[q][1] = c1; S.lg[q][2] = c2; S.lg[q][3] = c3;
     }
 #ifdef PVT_STAMPS
-    st_p2 += zstamp() - tB;
+    t_ret = zstamp();
+    st_p2 += t_ret - tB;
+    if (contd) { n_cont++; st_cont += gap + (t_ret - tA); }
 #endif
     return covered;
   };
@@ -1041,25 +1065,39 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   double nd0 = A.dem[(size_t)nw * 4 + 0], nd1 = A.dem[(size_t)nw * 4 + 1];
   double nd2 = A.dem[(size_t)nw * 4 + 2], nd3 = A.dem[(size_t)nw * 4 + 3];
   int nanc = A.anc[nw], ncal = A.ord[nw];
+  // run lengths from the order launch (the fast prologue's instance, where the driver has them):
+  // loaded with the batch's records
+  const bool rrm = FAST && A.run_rem != nullptr;
+  int nrr = rrm ? A.run_rem[nw] : 0;
   int nw1 = task_at(64 + lane);
-  int carry = 0;                             // tasks of this batch a run of the last one placed
+  int carry = 0;                             // tasks from this batch on that a run of an earlier one placed (64 and more: whole batches)
   // The batch's log (WinRec; sup: epoch_final_kernel) goes to HBM at the head of the NEXT batch,
   // between the copy of that batch's prefetched records and the loads for the one after it (the
   // last batch's after the loop): the record wait at a batch head then has only operations a
   // whole batch old before it. Stored right after its batch, behind the loads just issued, the
   // log's stores were what the next head's vmcnt wait stood on.
+  // The log is a ring of ZW_LOGN positions, a task's entry at its chain position & (ZW_LOGN - 1):
+  // a run writes ahead of its batch, at most 64 + ZW_RMAX positions past the oldest unflushed one
+  // (everything before the current batch is flushed at its head), so it never laps the ring. A
+  // batch that a run covered whole walks nothing and is flushed like any other.
   // Hosts: a single task's winner writes its host at the task's position, a run's taking lanes at
-  // their first positions (run_bulk); every other position of the batch buffer holds ZW_SAME and
-  // takes the host of the last written position at or before it -- the run's taking lanes fill
-  // consecutive ranges in lane order, so that is its host. Positions before the first written one
-  // continue a run carried over the batch end: the host of the last batch's position 63 (fprev).
-  int fk = 0, ftw = 0, fcal = 0;             // the unflushed batch: entries, its tasks' tw / tcal
+  // their first positions (run_bulk); every other position of the ring holds ZW_SAME (a batch's
+  // slots are reset after its flush) and takes the host of the last written position at or before
+  // it -- the run's taking lanes fill consecutive ranges in lane order, so that is its host.
+  // Positions before the batch's first written one continue a run from an earlier batch: the
+  // host of the last batch's position 63 (fprev, handed on from batch to batch).
+#ifdef PVT_STAMPS
+  double pl[4] = {0.0, 0.0, 0.0, 0.0};       // the last batch's last demand row and anchor (Ec)
+  int panc = -1, prr = 0;
+#endif
+  int fk = 0, ftw = 0, fcal = 0, fkb = 0;    // the unflushed batch: entries, its tasks' tw / tcal, its ring slots
   int32_t fprev = 0;
-  S.lgid[lane] = ZW_SAME;
-  S.lgid[64 + lane] = ZW_SAME;
+  static_assert(ZW_LOGN % 64 == 0, "the ring holds whole batches");
+#pragma unroll
+  for (int q = 0; q < ZW_LOGN; q += 64) S.lgid[q + lane] = ZW_SAME;
   auto flush_log = [&]() {
     if (UNI(fk > 0)) {
-      const int32_t raw = S.lgid[lane];
+      const int32_t raw = S.lgid[fkb + lane];
       const uint64_t upto = __ballot(raw != ZW_SAME) & (lane == 63 ? ~0ull : ((2ull << lane) - 1ull));
       const int32_t from = __shfl(raw, upto ? 63 - __builtin_clzll(upto) : 0);
       const int32_t id = upto ? from : fprev;
@@ -1068,9 +1106,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         WinRec& e = A.wlog[ftw];
         e.s = 0.0;
         e.id = id;
-        e.a[0] = S.lg[lane][0]; e.a[1] = S.lg[lane][1]; e.a[2] = S.lg[lane][2]; e.a[3] = S.lg[lane][3];
+        e.a[0] = S.lg[fkb + lane][0]; e.a[1] = S.lg[fkb + lane][1];
+        e.a[2] = S.lg[fkb + lane][2]; e.a[3] = S.lg[fkb + lane][3];
         A.placement[fcal] = id;
       }
+      S.lgid[fkb + lane] = ZW_SAME;          // (the slots' next batch starts from "as before")
     }
   };
   for (int i0 = 0; UNI(i0 < nt && !failed); i0 += 64) {
@@ -1083,17 +1123,21 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     const double td[4] = {nd0, nd1, nd2, nd3};
     const int tanc = nanc;
     const int tcal = ncal;
+    const int trr = nrr;
+    const int kb = i0 & (ZW_LOGN - 1);       // the batch's ring slots [kb, kb + 64)
     // (the record wait, explicit and ahead of the stores: left to the compiler it lands at the
     // records' first use, behind the flush, and waits for the stores just issued)
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
     __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0)
     __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    flush_log();                             // (before the carry shuffle below moves lg[64..])
-    if (i0 + 64 < nt) {                      // (uniform) batch b + 1's records, b + 2's positions
+    flush_log();
+    __atomic_signal_fence(__ATOMIC_SEQ_CST);   // (this batch's runs may write the slots just flushed)
+    if (i0 + 64 < nt) {                     // (uniform) batch b + 1's records, b + 2's positions
       nw = nw1;
       nd0 = A.dem[(size_t)nw * 4 + 0]; nd1 = A.dem[(size_t)nw * 4 + 1];
       nd2 = A.dem[(size_t)nw * 4 + 2]; nd3 = A.dem[(size_t)nw * 4 + 3];
       nanc = A.anc[nw]; ncal = A.ord[nw];
+      if (rrm) nrr = A.run_rem[nw];
       nw1 = task_at(i0 + 128 + lane);
     }
     const int kn = min(64, nt - i0);
@@ -1102,8 +1146,9 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     bool uni = __ballot(lane < kn && tanc != cur) == 0;
     // runs: bit i is set iff task i of the batch has task i - 1's demand vector, bit for bit (the
     // trace has few distinct demand rows, and sorted order puts equal ones next to each other)
-    uint64_t E;
-    {
+    // (not evaluated where the run lengths come with the records)
+    uint64_t E = 0;
+    if (!rrm) {
       bool same = lane > 0 && lane < kn;
 #pragma unroll
       for (int r = 0; r < 4; r++)
@@ -1113,10 +1158,27 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       // at its last copy of the run only, and the segment before must hold its own last copy)
       if (segm) E &= ~rfl_u64(S.sbits[i0 >> 6]);
     }
+#ifdef PVT_STAMPS
+    {                                        // E, and the batch's first task against the last batch's last
+      bool c0 = i0 > 0 && lane == 0 && tanc == panc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) c0 = c0 && __double_as_longlong(td[r]) == __double_as_longlong(pl[r]);
+      if (segm) c0 = c0 && !(rfl_u64(S.sbits[i0 >> 6]) & 1ull);
+      Ec = E | (__ballot(c0) & 1ull);
+      if (rrm) {                             // (the task before belongs to a stretch that goes on)
+        const int up = __shfl_up(trr, 1);
+        Ec = __ballot(lane < kn && (lane == 0 ? (i0 > 0 && prr >= 2) : up >= 2));
+        prr = readlane_i(trr, 63);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) pl[r] = readlane_d(td[r], 63);
+      panc = readlane_i(tanc, 63);
+    }
+#endif
     // A run that reaches the end of a full batch goes on into the next one while those tasks
     // have the same demand vector and anchor and no segment starts (their records are already in
-    // registers, nd*): at most 64 tasks per run, the ones past the batch logged at 64.. and
-    // carried (a third of the runs were cut at batch ends).
+    // registers, nd*): at most 64 tasks per run on this path, the ones past the batch logged
+    // ahead in the ring and counted in carry.
     int extc = -1;
     auto ext_len = [&]() -> int {
       if (extc < 0) {
@@ -1138,7 +1200,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       }
       return extc;
     };
+    // With the order launch's run lengths a run is the rest of its stretch of identical rows
+    // inside its group (so it ends at a segment start: the fast prologue's segments are whole
+    // groups, all of one anchor), ZW_RMAX tasks at the most; a longer one takes another call.
     auto run_len = [&](int k) {
+      if (rrm) return min(min(readlane_i(trr, k), ZW_RMAX), nt - i0 - k);
       int r = k < 63 ? min(kn - k, 1 + __builtin_ctzll(~(E >> (k + 1)))) : 1;
       if (k + r == 64) r = min(64, r + ext_len());
       return r;
@@ -1168,7 +1234,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (UNI(fm != 0)) {
           dirty = true;
           ZW_SEARCH_DONE();
-          return run_bulk(IntC<0>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, fm, R, k);
+          return run_bulk(IntC<0>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, fm, R, kb + k);
         }
         if (__ballot(((rvalid >> lane) & 1ull) && fits<STRICT>(ra0, ra1, ra2, ra3, mn[0], mn[1], mn[2], mn[3])))
           break;                               // chunk p0 can still take a task ahead
@@ -1188,7 +1254,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (UNI(fb != 0)) {
           bdirty = true;
           ZW_SEARCH_DONE();
-          return run_bulk(IntC<0>{}, rb0, rb1, rb2, rb3, bid, d0, d1, d2, d3, fb, R, k);
+          return run_bulk(IntC<0>{}, rb0, rb1, rb2, rb3, bid, d0, d1, d2, d3, fb, R, kb + k);
         }
       }
       for (int c = (pb >= 0 ? pb : p0) + 1; c < nch; c++) {
@@ -1206,7 +1272,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (!FF && UNI((fm & ~xzm) != 0)) return 0;
         if (UNI(fm != 0)) {
           ZW_SEARCH_DONE();
-          const int got = run_bulk(IntC<0>{}, x0, x1, x2, x3, xid, d0, d1, d2, d3, fm, R, k);
+          const int got = run_bulk(IntC<0>{}, x0, x1, x2, x3, xid, d0, d1, d2, d3, fm, R, kb + k);
           if (p < nwin) { S.wa[0][p] = x0; S.wa[1][p] = x1; S.wa[2][p] = x2; S.wa[3][p] = x3; }
           if (!KEYED && lane == 0) S.touch[c] = 1;
           return got;
@@ -1219,18 +1285,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #ifdef PVT_STAMPS
     st_batch += zstamp() - tb0;
 #endif
-    int k = carry;
-    {                                        // the carried run's log entries to their positions;
-      wave_lds_sync();                       // every other host entry back to "as before"
-      const int32_t cid = lane < carry ? S.lgid[64 + lane] : ZW_SAME;
-      if (lane < carry) {
-#pragma unroll
-        for (int r = 0; r < 4; r++) S.lg[lane][r] = S.lg[64 + lane][r];
-      }
-      S.lgid[lane] = cid;
-      S.lgid[64 + lane] = ZW_SAME;
-      wave_lds_sync();
-    }
+    int k = carry;                           // (>= kn: a run covered the batch whole, nothing to walk)
     while (UNI(k < kn)) {
       // (wave-uniform state the compiler cannot prove uniform: keeps the loops below scalar)
       k = __builtin_amdgcn_readfirstlane(k);
@@ -1256,8 +1311,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           if (UNI(m0 == 0 || (!FF && (fm0 & ~rzm) != 0))) break;
           // a run of tasks with this demand: placed in one pass over the chunk (run_bulk)
           const int R = run_len(k);
-          if (UNI(R >= 2)) {
-            const int c = run_bulk(IntC<1>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, m0, R, k);
+          if (UNI(R >= ZW_RMIN)) {
+            const int c = run_bulk(IntC<1>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, m0, R, kb + k);
             k += c;
             done += c;
             dirty = true;
@@ -1271,8 +1326,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           const bool win = __builtin_amdgcn_inverse_ballot_w64(m0 & (0ull - m0));
           ra0 = win ? n0 : ra0; ra1 = win ? n1 : ra1; ra2 = win ? n2 : ra2; ra3 = win ? n3 : ra3;
           if (win) {
-            S.lg[k][0] = n0; S.lg[k][1] = n1; S.lg[k][2] = n2; S.lg[k][3] = n3;
-            S.lgid[k] = rid;
+            S.lg[kb + k][0] = n0; S.lg[kb + k][1] = n1; S.lg[kb + k][2] = n2; S.lg[kb + k][3] = n3;
+            S.lgid[kb + k] = rid;
           }
           dirty = true;
 #ifdef PVT_STAMPS
@@ -1357,8 +1412,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         const bool win = __builtin_amdgcn_inverse_ballot_w64(m0 & (0ull - m0));
         ra0 = win ? n0 : ra0; ra1 = win ? n1 : ra1; ra2 = win ? n2 : ra2; ra3 = win ? n3 : ra3;
         if (win) {
-          S.lg[k][0] = n0; S.lg[k][1] = n1; S.lg[k][2] = n2; S.lg[k][3] = n3;
-          S.lgid[k] = rid;
+          S.lg[kb + k][0] = n0; S.lg[kb + k][1] = n1; S.lg[kb + k][2] = n2; S.lg[kb + k][3] = n3;
+          S.lgid[kb + k] = rid;
         }
         dirty = true;
       } else {
@@ -1373,8 +1428,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
             const bool win = __builtin_amdgcn_inverse_ballot_w64(mb & (0ull - mb));
             rb0 = win ? q0 : rb0; rb1 = win ? q1 : rb1; rb2 = win ? q2 : rb2; rb3 = win ? q3 : rb3;
             if (win) {
-              S.lg[k][0] = q0; S.lg[k][1] = q1; S.lg[k][2] = q2; S.lg[k][3] = q3;
-              S.lgid[k] = bid;
+              S.lg[kb + k][0] = q0; S.lg[kb + k][1] = q1; S.lg[kb + k][2] = q2; S.lg[kb + k][3] = q3;
+              S.lgid[kb + k] = bid;
             }
             bdirty = true;
             inb = true;
@@ -1398,8 +1453,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
               const bool win = lane == __builtin_ctzll(m);
               ra0 = win ? g0 : ra0; ra1 = win ? g1 : ra1; ra2 = win ? g2 : ra2; ra3 = win ? g3 : ra3;
               if (win) {
-                S.lg[k][0] = g0; S.lg[k][1] = g1; S.lg[k][2] = g2; S.lg[k][3] = g3;
-                S.lgid[k] = rid;
+                S.lg[kb + k][0] = g0; S.lg[kb + k][1] = g1; S.lg[kb + k][2] = g2; S.lg[kb + k][3] = g3;
+                S.lgid[kb + k] = rid;
               }
               dirty = true;
               found = true;
@@ -1433,8 +1488,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
                 if (lane == __builtin_ctzll(mc)) {
                   const double c0 = a0 - d0, c1 = a1 - d1, c2 = a2 - d2, c3 = a3 - d3;
                   S.wa[0][q] = c0; S.wa[1][q] = c1; S.wa[2][q] = c2; S.wa[3][q] = c3;
-                  S.lg[k][0] = c0; S.lg[k][1] = c1; S.lg[k][2] = c2; S.lg[k][3] = c3;
-                  S.lgid[k] = id;
+                  S.lg[kb + k][0] = c0; S.lg[kb + k][1] = c1; S.lg[kb + k][2] = c2; S.lg[kb + k][3] = c3;
+                  S.lgid[kb + k] = id;
                   if (!KEYED) S.touch[c] = 1;
                 }
                 found = true;
@@ -1457,7 +1512,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #ifdef PVT_STAMPS
     tb0 = zstamp();
 #endif
-    fk = __builtin_amdgcn_readfirstlane(k);
+    fk = __builtin_amdgcn_readfirstlane(min(k, kn));
+    fkb = kb;
     ftw = tw;
     fcal = tcal;
     carry = __builtin_amdgcn_readfirstlane(k > kn ? k - kn : 0);
@@ -1529,6 +1585,12 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     atomicAdd((unsigned long long*)&A.stamps[27], (unsigned long long)st_rep);
     atomicAdd((unsigned long long*)&A.stamps[28], (unsigned long long)n_cf);
     atomicAdd((unsigned long long*)&A.stamps[29], (unsigned long long)(t_load - t_start));
+    if (b < ZW_STAMP_CHAINS) {
+      uint64_t* pc = A.stamps + ZW_STAMP_CHAIN + 8 * b;
+      const uint64_t v[8] = {n_calls, n_cont, st_between, st_cont, t_end - t_walk, (uint64_t)done,
+                             (uint64_t)nt, 0};
+      for (int q = 0; q < 8; q++) atomicAdd((unsigned long long*)&pc[q], (unsigned long long)v[q]);
+    }
   }
 #endif
 }

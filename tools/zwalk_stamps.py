@@ -19,13 +19,15 @@ mode = sys.argv[4] if len(sys.argv) > 4 else "ca_bf"
 eng = PlacementEngine(0, lib_path=os.path.join(ROOT, "pivot-scheduling_amd", "diag", lib))
 f = eng.lib.pvt_debug_commit_stamps
 f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-buf = (ctypes.c_uint64 * 32)()
-assert f(eng.ctx, buf, 32) == 0
+CHAIN0, CHAINS = 32 + 4096, 64     # ZW_STAMP_CHAIN, ZW_STAMP_CHAINS (csrc/pvt_kernels.h)
+NW = CHAIN0 + 8 * CHAINS
+buf = (ctypes.c_uint64 * NW)()
+assert f(eng.ctx, buf, NW) == 0
 r = synthetic.make_round(MODES[mode], H, T)
 dr = DeviceRound(r, eng.device)
 eng.run(dr)
 torch.cuda.synchronize()
-assert f(eng.ctx, buf, 32) == 0
+assert f(eng.ctx, buf, NW) == 0
 st = eng.epoch_stats()
 nch = max(st["frontier_chains"] + st["list_chains"], 1)
 print("%s H=%d T=%d stats=%s" % (mode, H, T, st))
@@ -62,3 +64,14 @@ print("    calls with a partial lane: %d of %d, mean asg %.1f; calls that replay
 print("    runs counted in closed form: %d of %d" % (buf[28], buf[6]))
 print("  batches    %10.0f cycles per task (records, run masks, log flush)" % (buf[12] / max(buf[3], 1)))
 print("  single     %10d tasks on the one-task hot path" % buf[13])
+# per chain: run_bulk calls; those that continued a run a cap had cut (the task before the call's
+# first has the same demand row, anchor and segment); the cycles from one call's return to the next
+# one's entry (hot-loop re-entry, run length, batch heads: what no other stamp covers); and what the
+# continued calls cost in all, each from the return before it to its own return
+print("  per chain: tasks, walk cycles, run_bulk calls, continued, between-calls cycles (per call), continued calls' cycles (per call)")
+for c in range(CHAINS):
+    w = [int(x) for x in buf[CHAIN0 + 8 * c: CHAIN0 + 8 * c + 8]]
+    if w[6] == 0:
+        continue
+    print("    chain %2d: %5d of %5d tasks, walk %8d, calls %4d, continued %3d, between %8d (%5.0f), continued cost %8d (%5.0f)"
+          % (c, w[5], w[6], w[4], w[0], w[1], w[2], w[2] / max(w[0], 1), w[3], w[3] / max(w[1], 1)))
