@@ -55,6 +55,7 @@
 #include "pivot_place.h"
 #include "pvt_device.h"
 #include "pvt_kernels.h"
+#include "pvt_zwalk_stamps.h"
 #include "pvt_zwin_dev.h"
 
 namespace pvt {
@@ -68,13 +69,6 @@ constexpr double ZW_BIG = 0x1p500;
 
 #ifndef PVT_ZW_UNROLL
 #define PVT_ZW_UNROLL 8
-#endif
-#ifndef PVT_ZW_CF
-// run_bulk pass 1 in certified closed form (copies_cf): correct (t_zw green with it on) but not
-// faster -- config 5 ca_bf 0.218 vs 0.210-0.215 ms, 243 of 360 runs certified; the quotient,
-// the exponent tests and the certification cost about what the copy-by-copy pass does for the
-// two iterations a run takes. Off by default, kept for A/B (-DPVT_ZW_CF=1).
-#define PVT_ZW_CF 0
 #endif
 constexpr int ZW_UNROLL = PVT_ZW_UNROLL;   // run_bulk pass 1: copies per stop check
 constexpr int ZW_SB = 64;                  // suffix-minimum batches (the last one holds the rest)
@@ -143,54 +137,16 @@ __global__ __launch_bounds__(256) void host_min_kernel(const double* avail, int 
   }
 }
 
-// Fit from the minimum residual min(a - d): a >= d (best-fit) or a > d (first-fit, strict) in
-// every dimension; exact in sign for finite values (certificate 3).
+// A compile-time integer as a function argument (run_bulk: the dimensions a run updates).
 template <int N> struct IntC { static constexpr int value = N; };
-
-// ---- closed-form copy counts (run_bulk pass 1) ----------------------------------------------
-// Copies of a demand d > 0 a capacity x takes, subtracting sequentially: c = the largest j with
-// fit(x_j), x_j = fl(x_{j-1} - d) (fit: x_j >= 0, or > 0 STRICT). In exact arithmetic that is
-// floor(x / d) (STRICT: ceil(x / d) - 1). The estimate k from an approximate quotient is certified
-// against the sequential values without computing them: e_j = x - j d exactly, and
-//  * "nice" pairs -- x and d multiples of a power of two Q with every x - j d (j <= k + 1) below
-//    2^53 Q in magnitude (cpu counts, whole MiB) -- subtract exactly: x_j == e_j, so fit(e_k) and
-//    !fit(e_{k+1}) decide;
-//  * otherwise |x_j - e_j| <= j 2^-53 (|x| + j d) (one rounding per subtraction, intermediates
-//    below |x| + j d): e_k and e_{k+1} must clear twice that bound on their side of 0.
-// Anything else is "unsure" and the caller subtracts copy by copy. (x >= d > 0 here: the lane
-// fits one copy; counts are capped at ZW_CAP, more than any run takes.)
-constexpr int ZW_CAP = 256;
-__device__ __forceinline__ int lowbit_exp(double v) {   // exponent of v's lowest set bit (0: big)
-  const uint64_t b = (uint64_t)__double_as_longlong(v);
-  const uint64_t m = b & ((1ull << 52) - 1);
-  const int e = (int)((b >> 52) & 0x7ff);
-  if (e == 0) return m ? -1074 + __builtin_ctzll(m) : 4096;
-  return (e - 1075) + __builtin_ctzll(m | (1ull << 52));
-}
-__device__ __forceinline__ int high_exp(double v) {     // floor(log2 |v|) for normal v > 0
-  return (int)(((uint64_t)__double_as_longlong(v) >> 52) & 0x7ff) - 1023;
-}
-template <bool STRICT>
-__device__ __forceinline__ int copies_cf(double x, double d, bool& sure) {
-  if (__double_as_longlong(d) == 0) return ZW_CAP;      // (+0: the dimension never binds)
-  const double q = x * __builtin_amdgcn_rcp(d);
-  double kf = STRICT ? __builtin_ceil(q) - 1.0 : __builtin_floor(q);
-  kf = __builtin_fmin(kf, (double)ZW_CAP);
-  const double e0 = __builtin_fma(-kf, d, x), e1 = __builtin_fma(-(kf + 1.0), d, x);
-  const double big = __builtin_fabs(x) + (kf + 1.0) * d;
-  const bool nice = high_exp(big) + 2 <= min(lowbit_exp(x), lowbit_exp(d)) + 53;
-  const double err = nice ? 0.0 : (kf + 2.0) * 0x1p-52 * (big + d);
-  const bool fit0 = STRICT ? (e0 > err) : (e0 >= err && (nice || e0 > err));
-  const bool out1 = kf >= (double)ZW_CAP || (STRICT ? (e1 <= -err && (nice || e1 < -err)) : (e1 < -err));
-  sure = sure && kf >= 1.0 && fit0 && out1 && (q == q);
-  return (int)kf;
-}
 
 // A branch condition the wave holds uniformly: through readfirstlane, so that the compiler's
 // divergence analysis (which loses track across this walk's nested loops) keeps the branch scalar
 // instead of building exec-mask loops around it.
 #define UNI(c) (__builtin_amdgcn_readfirstlane((int)(c)) != 0)
 
+// Fit from the minimum residual min(a - d): a >= d (best-fit) or a > d (first-fit, strict) in
+// every dimension; exact in sign for finite values (certificate 3).
 template <bool STRICT>
 __device__ __forceinline__ bool fit_res(double m) { return STRICT ? (m > 0.0) : (m >= 0.0); }
 
@@ -210,15 +166,178 @@ __device__ __forceinline__ void compact_zone_window(const int32_t* zone, int Z, 
   compact_zone_window_t<WM, ZW_THREADS, ZW_SCAN>(zone, Z, U, h_lo, h_hi, wid, wz, cnt, nwin);
 }
 
-#ifdef PVT_STAMPS
-__device__ __forceinline__ uint64_t zstamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
+// The winner's log entry: its host and its capacities after the commit, at the task's ring slot.
+template <int WM>
+__device__ __forceinline__ void zw_log_entry(ZwalkLDS<WM>& S, int q, int32_t id, double a0, double a1,
+                                             double a2, double a3) {
+  S.lg[q][0] = a0; S.lg[q][1] = a1; S.lg[q][2] = a2; S.lg[q][3] = a3;
+  S.lgid[q] = id;
 }
-#endif
+
+// A run of R tasks with the same demand d from batch task k, placed on one 64-host chunk
+// (registers c0..c3, host cid; m0 = its lanes that fit d, all of them zero-cost). Sequentially
+// each task takes the lowest fitting lane; a lane that no longer fits d never fits it again
+// (capacities only fall), and the lanes that do not fit now never will, so the run fills the
+// fitting lanes in index order, each until it cannot take another copy of d. Pass 1: every
+// lane subtracts d again and again in parallel (cnt = copies taken; the active set only
+// shrinks), until the lanes up to the lowest active one u have taken R copies (fb = copies of
+// the finished lanes below u, u itself has taken t) or no lane takes another. Lane l then takes
+// asg = clamp(R - (copies of the lanes before it), 0, cnt) tasks; pass 2 leaves the chunk's
+// registers at the capacities after exactly those subtractions (from pass 1's snapshot of the
+// lane plus at most a block's copies, or replayed from the start) and logs them at the batch
+// position of the lane's last task. Returns the tasks placed (>= 1; fewer than R when the chunk runs
+// out). Bit-exact: the same sequential subtractions as one task after the other.
+// (One body for all four call sites; the closed-form counts of c05054d were compiled into the
+// hot loop's call only: a copy at each of the four call sites ran the walk out of scalar registers)
+template <bool STRICT, int WM>
+__device__ __forceinline__ int zw_run_bulk(ZwalkLDS<WM>& S, ZwStamps& st, double& c0, double& c1, double& c2,
+                                           double& c3, int32_t cid, double d0, double d1, double d2,
+                                           double d3, uint64_t m0, int R, int k) {
+  st.bulk_enter(k);
+  // (Dimensions of demand +0 keep their capacity, x - +0 == x bit for bit, and fit as they did
+  // for m0: with d2 = d3 = +0, the trace's disk and gpus, only cpus and memory are counted and
+  // updated.)
+  if (!(d0 >= 0.0 && d1 >= 0.0 && d2 >= 0.0 && d3 >= 0.0)) R = 1;   // (then one task only)
+  const bool on1 = __builtin_amdgcn_inverse_ballot_w64(m0);
+  const bool two = __double_as_longlong(d2) == 0 && __double_as_longlong(d3) == 0;
+  R = __builtin_amdgcn_readfirstlane(R);
+  int cnt = 0;
+  st.bulk_setup_done();
+  double s0 = c0, s1 = c1, s2 = c2, s3 = c3;   // pass 1's snapshots (below; c until a block start takes one)
+  int t = 0;                               // copies pass 1 has subtracted
+  // Pass 1: without per-lane masks: with d >= 0 a lane that fails a copy fails every later
+  // one (its residual only falls further), so every lane just keeps subtracting, counting
+  // the copies that fit (= the copies it takes); lanes outside m0 start at -inf.
+  // ZW_UNROLL copies per check (a check past the stop only raises counts of lanes that get no
+  // task or no more tasks: asg clamps them).
+  // The loop is bound by issue, not by latency (tools/f64_chain.hip: a dependent v_add_f64
+  // link is 9 cycles, an instruction of a lone wave issues every ~5), so a copy costs its
+  // instructions: the subtractions, the minima, one compare and one carry add -- a copy that
+  // fits adds one to cnt (exact: a lane that fails a copy fails every later one, so its
+  // count is the number of copies that fit). The copies of a block are software-pipelined in
+  // the source (subtractions of copy j, pair minima of j - 1, last minimum of j - 2, test of
+  // j - 3) and pinned by scheduling barriers, so that no instruction waits for the one
+  // before it. Left alone the compiler puts each minimum and compare right behind what it
+  // reads.
+  // Snapshots for pass 2: s = the capacities at the last block start at which the lane still
+  // fit every copy so far (two selects per changing dimension per block, not per copy).
+  double x0 = on1 ? c0 : -DINF, x1 = on1 ? c1 : -DINF, x2 = on1 ? c2 : -DINF, x3 = on1 ? c3 : -DINF;
+  auto pass1 = [&](auto dims) {
+    constexpr int D = decltype(dims)::value;
+    constexpr int U = ZW_UNROLL;
+    int u = __builtin_ctzll(m0), fb = 0;
+    bool f = false;
+    for (;;) {
+      t = __builtin_amdgcn_readfirstlane(t);
+      u = __builtin_amdgcn_readfirstlane(u);
+      fb = __builtin_amdgcn_readfirstlane(fb);
+      if (t > 0) {                           // (f: the lane took the last block's last copy)
+        s0 = f ? x0 : s0; s1 = f ? x1 : s1;
+        if (D == 4) { s2 = f ? x2 : s2; s3 = f ? x3 : s3; }
+      }
+      double a0[U], a1[U], a2[U], a3[U], mp[U], mq[U], mm[U];
+#pragma unroll
+      for (int j = 0; j < U + 3; j++) {
+        if (j < U) {
+          a0[j] = (j ? a0[j - 1] : x0) - d0;
+          a1[j] = (j ? a1[j - 1] : x1) - d1;
+          if (D == 4) { a2[j] = (j ? a2[j - 1] : x2) - d2; a3[j] = (j ? a3[j - 1] : x3) - d3; }
+        }
+        if (j >= 1 && j - 1 < U) {
+          mp[j - 1] = fmin(a0[j - 1], a1[j - 1]);
+          if (D == 4) mq[j - 1] = fmin(a2[j - 1], a3[j - 1]);
+        }
+        if (j >= 2 && j - 2 < U) mm[j - 2] = D == 4 ? fmin(mp[j - 2], mq[j - 2]) : mp[j - 2];
+        if (j >= 3) {
+          f = fit_res<STRICT>(mm[j - 3]);
+          cnt += f ? 1 : 0;
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      x0 = a0[U - 1]; x1 = a1[U - 1];
+      if (D == 4) { x2 = a2[U - 1]; x3 = a3[U - 1]; }
+      t += ZW_UNROLL;
+      // (the stop tests on scalars: a ballot through rfl_u64, t / u / fb / R through
+      // readfirstlane -- plain scalar compares, no round trip through a vector register)
+      const uint64_t an = rfl_u64(__ballot(f));   // lanes that took copy t
+      if (an == 0) break;
+      const int un = __builtin_ctzll(an);
+      if (un != u) {                         // (u only rises: every lane below un is done)
+        u = un;
+        fb = __builtin_amdgcn_readlane(wave_incl_scan_dpp(cnt), u - 1);
+      }
+      if (fb + t >= R) break;
+    }
+  };
+  if (two) pass1(IntC<2>{});
+  else pass1(IntC<4>{});
+  st.bulk_pass1_done(t);
+  const int incl = wave_incl_scan_dpp(cnt);
+  const int pre = incl - cnt;
+  const int asg = max(0, min(cnt, R - pre));
+  const int covered = min(R, __builtin_amdgcn_readlane(incl, 63));
+  st.bulk_counted();
+  // Pass 2: a taking lane marks its host and ends at its capacities after asg copies: the same
+  // sequential subtractions as task after task, so bit-exact. Pass 1 held most of them: the
+  // snapshot s is the lane's value after sbc copies, sbc = the last block start it was still
+  // whole at (the largest multiple of ZW_UNROLL up to cnt, at most the last block's start).
+  // A lane with asg >= sbc -- every lane that takes all its copies, and the last taking lane
+  // when the run ends in the block that stopped pass 1 -- goes on from s with asg - sbc copies,
+  // at most a block's (x - d by v_add_f64 and fma(-1, d, x) round once to the same value);
+  // a lane that takes fewer copies than its snapshot holds (at most one per call: the last
+  // taking lane) replays its asg copies from c. A lane that takes nothing has sbc > 0 = asg or
+  // s == c: it keeps c. The log keeps the host of
+  // every copy and the capacities after a lane's last one only: a host's earlier entries in a
+  // segment are never final (epoch_final_kernel marks them; validation and apply read the
+  // capacities of final entries only, and the keyed / ordered walks read no log).
+  // (each taking lane writes its host at its first run position only; the positions after it
+  // keep the batch's "as before" mark, ZW_SAME, and the flush gives each the host of the last
+  // written position at or before it -- once per batch, not once per run)
+  if (asg > 0) S.lgid[(k + pre) & (ZW_LOGN - 1)] = cid;
+  const int sbc = min(cnt / ZW_UNROLL * ZW_UNROLL, max(t - ZW_UNROLL, 0));
+  const bool snap = asg >= sbc;
+  const int nrep = snap ? asg - sbc : asg;
+  c0 = snap ? s0 : c0; c1 = snap ? s1 : c1;
+  c2 = snap ? s2 : c2; c3 = snap ? s3 : c3;  // (two: s2 == c2, s3 == c3)
+  // the copies left, a scalar: at most a block's from a snapshot (4 or 8: one ballot), and the
+  // count of the one lane that starts over, if any
+  const uint64_t over = rfl_u64(__ballot(asg > 0 && !snap));
+  int nmax = rfl_u64(__ballot(snap && nrep > 4)) ? ZW_UNROLL : rfl_u64(__ballot(snap && nrep > 0)) ? 4 : 0;
+  if (over) nmax = max(nmax, __builtin_amdgcn_readlane(asg, __builtin_ctzll(over)));
+  st.bulk_assigned(asg, cnt, over);
+  // (c - d as fma(-1, d, c), rounded once, the same bits; fma(-0, d, c) == c for the finite d
+  // and c of a proven chain: one 0/1 factor per copy for every dimension)
+  if (two) {
+    for (int m = 0; m < nmax; m += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const double o = m + u < nrep ? -1.0 : -0.0;
+        c0 = __builtin_fma(o, d0, c0);
+        c1 = __builtin_fma(o, d1, c1);
+      }
+      st.bulk_replay_block();
+    }
+  } else {
+    for (int m = 0; m < nmax; m += 4) {
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const double o = m + u < nrep ? -1.0 : -0.0;
+        c0 = __builtin_fma(o, d0, c0);
+        c1 = __builtin_fma(o, d1, c1);
+        c2 = __builtin_fma(o, d2, c2);
+        c3 = __builtin_fma(o, d3, c3);
+      }
+      st.bulk_replay_block();
+    }
+  }
+  st.bulk_replayed();
+  if (asg > 0) {
+    const int q = (k + pre + asg - 1) & (ZW_LOGN - 1);
+    S.lg[q][0] = c0; S.lg[q][1] = c1; S.lg[q][2] = c2; S.lg[q][3] = c3;
+  }
+  st.bulk_exit();
+  return covered;
+}
 
 // KEYED: cost_aware first-fit with sort_hosts (the driver's round_next_window): one group, its
 // window the first ZW_M hosts of the group's zero-key prefix (perm, index order), strict fit,
@@ -233,19 +352,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   static_assert(!FF || (!KEYED && STRICT), "FF: chain mode, strict fit");
   static_assert(WM == ZW_M || !KEYED, "keyed / ordered / sharded windows: ZW_M hosts");
   __shared__ ZwalkLDS<WM> S;
-#ifdef PVT_STAMPS
-  const uint64_t t_start = zstamp();
-  uint64_t n_chunks = 0, n_switch = 0, n_bulk = 0, n_runs = 0;
-  uint64_t st_search = 0, st_p1 = 0, st_p2 = 0, n_probe = 0, n_iter = 0, st_batch = 0, n_single = 0;
-  uint64_t st_setup = 0, st_loop = 0, st_who = 0, st_rep = 0;   // run_bulk's parts
-  uint64_t n_cf = 0;                                              // runs counted in closed form
-  uint64_t n_part = 0, s_pasg = 0, n_fromc = 0, n_rep = 0;       // pass 2: calls with a partial lane, its asg; replays from c; copies
-  // per chain (ZW_STAMP_CHAIN): run_bulk calls; those that continue a run a cap cut (the task
-  // before the call's first has its demand row, anchor and segment: Ec, per batch); the cycles
-  // between one call's return and the next one's entry; a continued call's cost from the return
-  // before it to its own
-  uint64_t n_calls = 0, n_cont = 0, st_between = 0, st_cont = 0, t_ret = 0, Ec = 0;
-#endif
+  ZwStamps st;
+  st.start();
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // chain tables: by value in the arguments (A.tab; the host sends them only for chains of at
   // most CHAIN_MAX tasks, as the epoch planner builds them), or device arrays (uploaded)
@@ -258,7 +366,6 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   // flat load per access -- nor one computed from the segments per access: the walk ran 4-7 %
   // slower either way.)
   const int32_t* gcmap = KEYED ? nullptr : A.cmap + base;
-  auto cmap_at = [&](int i) -> int { return gcmap[i]; };
   const bool segm = !KEYED && (tabm || A.cseg);   // group segment starts break runs
   int32_t* status = A.status + 2 * b;
   const int Z = A.Z, H = A.H;
@@ -293,9 +400,6 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   double mn[4];                              // (the walk: the batch's minima ahead)
   uint32_t U;                                // the window's zone set (certificate 2)
   int nwin;
-#ifdef PVT_STAMPS
-  uint64_t t_load, t_cert, t_win, t_cap;
-#endif
   if constexpr (FAST) {
     // ---- The fast prologue (ChainCert): an unsharded best-fit chain of the
     // round's first epoch, tables by value, every segment a whole group with a certificate
@@ -398,9 +502,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       for (int r = 0; r < 4; r++) S.red[wave][8 + r] = ha[r];
       S.cnt[0][wave] = wbadv ? 1 : 0;
     }
-#ifdef PVT_STAMPS
-    t_load = zstamp();
-#endif
+    st.loaded();
     __syncthreads();
     if (tid < Z) {                             // anchor row -> zero-cost zone mask
       uint32_t m = 0;
@@ -440,9 +542,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // (it never walks a window it has not verified: the host's zone set inside the window's)
     const bool cover = zu != 0 && (A.cert.cu[b] & ~zu) == 0;
     const bool stop = bad || !sep || nt <= 0 || nt > CHAIN_MAX || !cover || zbad != 0 || nwin <= 0;
-#ifdef PVT_STAMPS
-    t_cert = t_win = t_cap = zstamp();
-#endif
+    st.certified_fast();
     __syncthreads();
     if (tid == 0) {
       int cert = stop ? 0 : ZW_CERT_FAST;
@@ -514,9 +614,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (tid == 0) { S.umask = 0; S.nwin = 0; S.bail = 0; }
     if (tid < CHAIN_MAX / 64) S.sbits[tid] = 0;
     if (tid < WM / 64) S.touch[tid] = 0;
-#ifdef PVT_STAMPS
-    t_load = zstamp();
-#endif
+    st.loaded();
     __syncthreads();
     if (!KEYED && tid < Z) {                   // anchor row -> zero-cost zone mask
       uint32_t m = 0;
@@ -556,7 +654,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #pragma unroll
       for (int u = 0; u < ZW_PR; u++) {
         const int i = i0 + ZW_PR * ZW_THREADS + u * ZW_THREADS + tid;
-        wn[u] = i < nt ? (KEYED ? i : cmap_at(i)) : -1;
+        wn[u] = i < nt ? (KEYED ? i : gcmap[i]) : -1;
       }
 #pragma unroll
       for (int u = 0; u < ZW_PR; u++) {
@@ -608,9 +706,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (bad) S.bail = 1;                        // benign race: every writer stores 1
     if (um) atomicOr(&S.umask, um);
     __syncthreads();
-#ifdef PVT_STAMPS
-    t_cert = zstamp();
-#endif
+    st.certified();
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       for (int w = 1; w < ZW_WAVES; w++) {
@@ -682,9 +778,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       compact_zone_window<WM>(A.zone, Z, U, 0, H, S.wid, S.wz, S.cnt, &S.nwin);
     }
     nwin = S.nwin;
-#ifdef PVT_STAMPS
-    t_win = zstamp();
-#endif
+    st.window_built();
     bool wbad = false;
     // optimistic apply: the window's hosts and start capacities, saved for an undo (plain stores
     // nothing waits for)
@@ -721,9 +815,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     }
     if (wbad) S.bail = 1;
     __syncthreads();
-#ifdef PVT_STAMPS
-    t_cap = zstamp();
-#endif
+    st.capacities_loaded();
     if (S.bail || nwin == 0) {
       if (tid == 0) report(0, KEYED ? 0 : 1);
       return;
@@ -736,7 +828,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       const int i1 = blk == ZW_SB - 1 ? nt : min(nt, blk * 64 + 64);
       double bm[4] = {DINF, DINF, DINF, DINF};
       for (int i = blk * 64 + lane; i < i1; i += 64) {
-        const int w = KEYED ? i : cmap_at(i);
+        const int w = KEYED ? i : gcmap[i];
 #pragma unroll
         for (int r = 0; r < 4; r++) bm[r] = fmin(bm[r], A.dem[(size_t)w * 4 + r]);
       }
@@ -758,9 +850,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     __syncthreads();
   }
   if (wave != 0) return;
-#ifdef PVT_STAMPS
-  const uint64_t t_walk = zstamp();
-#endif
+  st.walk_begins();
 
   // ---- the walk (one wave). Lane l of chunk c holds window host c * 64 + l. Chunk p0 (the
   // first that can still fit a chain task) stays in registers, where nearly every task finds its
@@ -816,251 +906,12 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (bdirty && pb >= 0 && p < nwin) { S.wa[0][p] = rb0; S.wa[1][p] = rb1; S.wa[2][p] = rb2; S.wa[3][p] = rb3; }
     bdirty = false;
   };
-  // A run of R tasks with the same demand d from batch task k, placed on one 64-host chunk
-  // (registers c0..c3, host cid; m0 = its lanes that fit d, all of them zero-cost). Sequentially
-  // each task takes the lowest fitting lane; a lane that no longer fits d never fits it again
-  // (capacities only fall), and the lanes that do not fit now never will, so the run fills the
-  // fitting lanes in index order, each until it cannot take another copy of d. Pass 1: every
-  // lane subtracts d again and again in parallel (cnt = copies taken; the active set only
-  // shrinks), until the lanes up to the lowest active one u have taken R copies (fb = copies of
-  // the finished lanes below u, u itself has taken t) or no lane takes another. Lane l then takes
-  // asg = clamp(R - (copies of the lanes before it), 0, cnt) tasks; pass 2 leaves the chunk's
-  // registers at the capacities after exactly those subtractions (from pass 1's snapshot of the
-  // lane plus at most a block's copies, or replayed from the start) and logs them at the batch
-  // position of the lane's last task. Returns the tasks placed (>= 1; fewer than R when the chunk runs
-  // out). Bit-exact: the same sequential subtractions as one task after the other.
-  // (CFT: IntC<1> where the closed-form counts are compiled in -- the hot loop's call only: a
-  // copy at each of the four call sites ran the walk out of scalar registers)
-  auto run_bulk = [&](auto cft, double& c0, double& c1, double& c2, double& c3, int32_t cid, double d0,
-                      double d1, double d2, double d3, uint64_t m0, int R, int k) -> int {
-#ifdef PVT_STAMPS
-    const uint64_t tA = zstamp();
-    const uint64_t gap = t_ret ? tA - t_ret : 0;
-    const bool contd = (Ec >> (k & 63)) & 1ull;
-    n_calls++;
-    st_between += gap;
-#endif
-    // (Dimensions of demand +0 keep their capacity, x - +0 == x bit for bit, and fit as they did
-    // for m0: with d2 = d3 = +0, the trace's disk and gpus, only cpus and memory are counted and
-    // updated.)
-    if (!(d0 >= 0.0 && d1 >= 0.0 && d2 >= 0.0 && d3 >= 0.0)) R = 1;   // (then one task only)
-    const bool on1 = __builtin_amdgcn_inverse_ballot_w64(m0);
-    const bool two = __double_as_longlong(d2) == 0 && __double_as_longlong(d3) == 0;
-    R = __builtin_amdgcn_readfirstlane(R);
-    int cnt = 0;
-#ifdef PVT_STAMPS
-    const uint64_t tA1 = zstamp();
-    st_setup += tA1 - tA;
-#endif
-    bool cf = false;                         // the closed-form counts are certified
-    double s0 = c0, s1 = c1, s2 = c2, s3 = c3;   // pass 1's snapshots (below; c until a block start takes one)
-    int t = 0;                               // copies pass 1 has subtracted (0: it did not run)
-#if PVT_ZW_CF
-    if (decltype(cft)::value && R >= 2) {
-      // Pass 1 in closed form (copies_cf): every lane of m0 counts its copies from a quotient,
-      // certified per dimension; uncertain lanes only matter if the lanes before them do not
-      // cover the run (then the copy-by-copy pass below decides)
-      bool sure = true;
-      int k = ZW_CAP;
-      if (on1) {
-        k = min(copies_cf<STRICT>(c0, d0, sure), copies_cf<STRICT>(c1, d1, sure));
-        if (!two) k = min(k, min(copies_cf<STRICT>(c2, d2, sure), copies_cf<STRICT>(c3, d3, sure)));
-      }
-      const bool bad = on1 && !sure;
-      const uint64_t ub = __ballot(bad);
-      const int kc = on1 && sure ? k : 0;
-      const int inc = wave_incl_scan_dpp(kc);
-      const int first_bad = ub ? __builtin_ctzll(ub) : 64;
-      const int before_bad = first_bad == 0 ? 0 : __builtin_amdgcn_readlane(inc, first_bad - 1);
-      cf = ub == 0 || before_bad >= R;
-      if (cf) cnt = (lane < first_bad) ? kc : 0;
-#ifdef PVT_STAMPS
-      n_cf += cf;
-#endif
-    }
-#endif
-    if (!cf) {
-      // Pass 1: without per-lane masks: with d >= 0 a lane that fails a copy fails every later
-      // one (its residual only falls further), so every lane just keeps subtracting, counting
-      // the copies that fit (= the copies it takes); lanes outside m0 start at -inf.
-      // ZW_UNROLL copies per check (a check past the stop only raises counts of lanes that get no
-      // task or no more tasks: asg clamps them).
-      // The loop is bound by issue, not by latency (tools/f64_chain.hip: a dependent v_add_f64
-      // link is 9 cycles, an instruction of a lone wave issues every ~5), so a copy costs its
-      // instructions: the subtractions, the minima, one compare and one carry add -- a copy that
-      // fits adds one to cnt (exact: a lane that fails a copy fails every later one, so its
-      // count is the number of copies that fit). The copies of a block are software-pipelined in
-      // the source (subtractions of copy j, pair minima of j - 1, last minimum of j - 2, test of
-      // j - 3) and pinned by scheduling barriers, so that no instruction waits for the one
-      // before it. Left alone the compiler puts each minimum and compare right behind what it
-      // reads.
-      // Snapshots for pass 2: s = the capacities at the last block start at which the lane still
-      // fit every copy so far (two selects per changing dimension per block, not per copy).
-      double x0 = on1 ? c0 : -DINF, x1 = on1 ? c1 : -DINF, x2 = on1 ? c2 : -DINF, x3 = on1 ? c3 : -DINF;
-      auto pass1 = [&](auto dims) {
-        constexpr int D = decltype(dims)::value;
-        constexpr int U = ZW_UNROLL;
-        int u = __builtin_ctzll(m0), fb = 0;
-        bool f = false;
-        for (;;) {
-          t = __builtin_amdgcn_readfirstlane(t);
-          u = __builtin_amdgcn_readfirstlane(u);
-          fb = __builtin_amdgcn_readfirstlane(fb);
-          if (t > 0) {                           // (f: the lane took the last block's last copy)
-            s0 = f ? x0 : s0; s1 = f ? x1 : s1;
-            if (D == 4) { s2 = f ? x2 : s2; s3 = f ? x3 : s3; }
-          }
-          double a0[U], a1[U], a2[U], a3[U], mp[U], mq[U], mm[U];
-#pragma unroll
-          for (int j = 0; j < U + 3; j++) {
-            if (j < U) {
-              a0[j] = (j ? a0[j - 1] : x0) - d0;
-              a1[j] = (j ? a1[j - 1] : x1) - d1;
-              if (D == 4) { a2[j] = (j ? a2[j - 1] : x2) - d2; a3[j] = (j ? a3[j - 1] : x3) - d3; }
-            }
-            if (j >= 1 && j - 1 < U) {
-              mp[j - 1] = fmin(a0[j - 1], a1[j - 1]);
-              if (D == 4) mq[j - 1] = fmin(a2[j - 1], a3[j - 1]);
-            }
-            if (j >= 2 && j - 2 < U) mm[j - 2] = D == 4 ? fmin(mp[j - 2], mq[j - 2]) : mp[j - 2];
-            if (j >= 3) {
-              f = fit_res<STRICT>(mm[j - 3]);
-              cnt += f ? 1 : 0;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          x0 = a0[U - 1]; x1 = a1[U - 1];
-          if (D == 4) { x2 = a2[U - 1]; x3 = a3[U - 1]; }
-          t += ZW_UNROLL;
-          // (the stop tests on scalars: a ballot through rfl_u64, t / u / fb / R through
-          // readfirstlane -- plain scalar compares, no round trip through a vector register)
-          const uint64_t an = rfl_u64(__ballot(f));   // lanes that took copy t
-          if (an == 0) break;
-          const int un = __builtin_ctzll(an);
-          if (un != u) {                         // (u only rises: every lane below un is done)
-            u = un;
-            fb = __builtin_amdgcn_readlane(wave_incl_scan_dpp(cnt), u - 1);
-          }
-          if (fb + t >= R) break;
-        }
-      };
-      if (two) pass1(IntC<2>{});
-      else pass1(IntC<4>{});
-#ifdef PVT_STAMPS
-      n_iter += t;
-#endif
-    }
-#ifdef PVT_STAMPS
-    st_loop += zstamp() - tA1;
-#endif
-    const int incl = wave_incl_scan_dpp(cnt);
-    const int pre = incl - cnt;
-    const int asg = max(0, min(cnt, R - pre));
-    const int covered = min(R, __builtin_amdgcn_readlane(incl, 63));
-#ifdef PVT_STAMPS
-    const uint64_t tB = zstamp();
-    st_p1 += tB - tA;
-#endif
-    // Pass 2: a taking lane marks its host and ends at its capacities after asg copies: the same
-    // sequential subtractions as task after task, so bit-exact. Pass 1 held most of them: the
-    // snapshot s is the lane's value after sbc copies, sbc = the last block start it was still
-    // whole at (the largest multiple of ZW_UNROLL up to cnt, at most the last block's start).
-    // A lane with asg >= sbc -- every lane that takes all its copies, and the last taking lane
-    // when the run ends in the block that stopped pass 1 -- goes on from s with asg - sbc copies,
-    // at most a block's (x - d by v_add_f64 and fma(-1, d, x) round once to the same value);
-    // a lane that takes fewer copies than its snapshot holds (at most one per call: the last
-    // taking lane) replays its asg copies from c. A lane that takes nothing has sbc > 0 = asg or
-    // s == c: it keeps c. The log keeps the host of
-    // every copy and the capacities after a lane's last one only: a host's earlier entries in a
-    // segment are never final (epoch_final_kernel marks them; validation and apply read the
-    // capacities of final entries only, and the keyed / ordered walks read no log).
-    // (each taking lane writes its host at its first run position only; the positions after it
-    // keep the batch's "as before" mark, ZW_SAME, and the flush gives each the host of the last
-    // written position at or before it -- once per batch, not once per run)
-    if (asg > 0) S.lgid[(k + pre) & (ZW_LOGN - 1)] = cid;
-    const int sbc = min(cnt / ZW_UNROLL * ZW_UNROLL, max(t - ZW_UNROLL, 0));
-#ifdef PVT_ZW_REPLAY_FULL
-    const bool snap = false;                 // A/B: every lane replays its asg copies from c
-#else
-    const bool snap = asg >= sbc;
-#endif
-    const int nrep = snap ? asg - sbc : asg;
-    c0 = snap ? s0 : c0; c1 = snap ? s1 : c1;
-    c2 = snap ? s2 : c2; c3 = snap ? s3 : c3;  // (two: s2 == c2, s3 == c3)
-    // the copies left, a scalar: at most a block's from a snapshot (4 or 8: one ballot), and the
-    // count of the one lane that starts over, if any
-    const uint64_t over = rfl_u64(__ballot(asg > 0 && !snap));
-#ifdef PVT_ZW_REPLAY_FULL
-    (void)over;
-    const int nmax = wave_max_i32(asg);      // (every taking lane starts over)
-#else
-    int nmax = rfl_u64(__ballot(snap && nrep > 4)) ? ZW_UNROLL : rfl_u64(__ballot(snap && nrep > 0)) ? 4 : 0;
-    if (over) nmax = max(nmax, __builtin_amdgcn_readlane(asg, __builtin_ctzll(over)));
-#if PVT_ZW_CF
-    // (closed-form counts: pass 1 did not run, so s == c, sbc == 0 and every taking lane replays
-    // all its asg copies, which no block bounds)
-    if (cf) nmax = wave_max_i32(asg);
-#endif
-#endif
-#ifdef PVT_STAMPS
-    {
-      const uint64_t part = __ballot(asg > 0 && asg < cnt);
-      n_part += part != 0;
-      if (part) s_pasg += (uint64_t)__builtin_amdgcn_readlane(asg, __builtin_ctzll(part));
-      n_fromc += over != 0;
-    }
-    const uint64_t tC = zstamp();
-    st_who += tC - tB;
-#endif
-    // (c - d as fma(-1, d, c), rounded once, the same bits; fma(-0, d, c) == c for the finite d
-    // and c of a proven chain: one 0/1 factor per copy for every dimension)
-    if (two) {
-      for (int m = 0; m < nmax; m += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const double o = m + u < nrep ? -1.0 : -0.0;
-          c0 = __builtin_fma(o, d0, c0);
-          c1 = __builtin_fma(o, d1, c1);
-        }
-#ifdef PVT_STAMPS
-        n_rep += 4;
-#endif
-      }
-    } else {
-      for (int m = 0; m < nmax; m += 4) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-          const double o = m + u < nrep ? -1.0 : -0.0;
-          c0 = __builtin_fma(o, d0, c0);
-          c1 = __builtin_fma(o, d1, c1);
-          c2 = __builtin_fma(o, d2, c2);
-          c3 = __builtin_fma(o, d3, c3);
-        }
-#ifdef PVT_STAMPS
-        n_rep += 4;
-#endif
-      }
-    }
-#ifdef PVT_STAMPS
-    st_rep += zstamp() - tC;
-#endif
-    if (asg > 0) {
-      const int q = (k + pre + asg - 1) & (ZW_LOGN - 1);
-      S.lg[q][0] = c0; S.lg[q][1] = c1; S.lg[q][2] = c2; S.lg[q][3] = c3;
-    }
-#ifdef PVT_STAMPS
-    t_ret = zstamp();
-    st_p2 += t_ret - tB;
-    if (contd) { n_cont++; st_cont += gap + (t_ret - tA); }
-#endif
-    return covered;
-  };
   load_chunk(0);
   load_b(1);
   // task records, software-pipelined across 64-task batches: while batch b is walked, batch
   // b + 1's records and batch b + 2's chain positions are in flight (no HBM latency at a batch
   // start)
-  auto task_at = [&](int i) { return i < nt ? (KEYED ? i : cmap_at(i)) : 0; };
+  auto task_at = [&](int i) { return i < nt ? (KEYED ? i : gcmap[i]) : 0; };
   int nw = task_at(lane);
   double nd0 = A.dem[(size_t)nw * 4 + 0], nd1 = A.dem[(size_t)nw * 4 + 1];
   double nd2 = A.dem[(size_t)nw * 4 + 2], nd3 = A.dem[(size_t)nw * 4 + 3];
@@ -1086,10 +937,6 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   // it -- the run's taking lanes fill consecutive ranges in lane order, so that is its host.
   // Positions before the batch's first written one continue a run from an earlier batch: the
   // host of the last batch's position 63 (fprev, handed on from batch to batch).
-#ifdef PVT_STAMPS
-  double pl[4] = {0.0, 0.0, 0.0, 0.0};       // the last batch's last demand row and anchor (Ec)
-  int panc = -1, prr = 0;
-#endif
   int fk = 0, ftw = 0, fcal = 0, fkb = 0;    // the unflushed batch: entries, its tasks' tw / tcal, its ring slots
   int32_t fprev = 0;
   static_assert(ZW_LOGN % 64 == 0, "the ring holds whole batches");
@@ -1114,9 +961,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     }
   };
   for (int i0 = 0; UNI(i0 < nt && !failed); i0 += 64) {
-#ifdef PVT_STAMPS
-    uint64_t tb0 = zstamp();
-#endif
+    st.batch_part_begins();
 #pragma unroll
     for (int r = 0; r < 4; r++) mn[r] = S.smin[min(i0 >> 6, ZW_SB - 1)][r];
     const int tw = nw;
@@ -1158,23 +1003,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       // at its last copy of the run only, and the segment before must hold its own last copy)
       if (segm) E &= ~rfl_u64(S.sbits[i0 >> 6]);
     }
-#ifdef PVT_STAMPS
-    {                                        // E, and the batch's first task against the last batch's last
-      bool c0 = i0 > 0 && lane == 0 && tanc == panc;
-#pragma unroll
-      for (int r = 0; r < 4; r++) c0 = c0 && __double_as_longlong(td[r]) == __double_as_longlong(pl[r]);
-      if (segm) c0 = c0 && !(rfl_u64(S.sbits[i0 >> 6]) & 1ull);
-      Ec = E | (__ballot(c0) & 1ull);
-      if (rrm) {                             // (the task before belongs to a stretch that goes on)
-        const int up = __shfl_up(trr, 1);
-        Ec = __ballot(lane < kn && (lane == 0 ? (i0 > 0 && prr >= 2) : up >= 2));
-        prr = readlane_i(trr, 63);
-      }
-#pragma unroll
-      for (int r = 0; r < 4; r++) pl[r] = readlane_d(td[r], 63);
-      panc = readlane_i(tanc, 63);
-    }
-#endif
+    st.batch_runs(E, i0, kn, lane, td[0], td[1], td[2], td[3], tanc, trr, rrm, segm, S.sbits);
     // A run that reaches the end of a full batch goes on into the next one while those tasks
     // have the same demand vector and anchor and no segment starts (their records are already in
     // registers, nd*): at most 64 tasks per run on this path, the ones past the batch logged
@@ -1217,12 +1046,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // host of a chunk it looks at is outside the anchor's zero-cost zones (else 0: the per-task
     // path decides, with exact scores). Returns the tasks placed (0: none).
     auto run_step = [&](int k) -> int {
-#ifdef PVT_STAMPS
-      const uint64_t t0 = zstamp();
-#define ZW_SEARCH_DONE() (st_search += zstamp() - t0)
-#else
-#define ZW_SEARCH_DONE() ((void)0)
-#endif
+      st.search_begins();
       const double d0 = readlane_d(td[0], k), d1 = readlane_d(td[1], k);
       const double d2 = readlane_d(td[2], k), d3 = readlane_d(td[3], k);
       const int R = run_len(k);
@@ -1233,8 +1057,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (!FF && UNI((fm & ~rzm) != 0)) return 0;
         if (UNI(fm != 0)) {
           dirty = true;
-          ZW_SEARCH_DONE();
-          return run_bulk(IntC<0>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, fm, R, kb + k);
+          st.search_ends();
+          return zw_run_bulk<STRICT>(S, st, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, fm, R, kb + k);
         }
         if (__ballot(((rvalid >> lane) & 1ull) && fits<STRICT>(ra0, ra1, ra2, ra3, mn[0], mn[1], mn[2], mn[3])))
           break;                               // chunk p0 can still take a task ahead
@@ -1253,8 +1077,8 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (!FF && UNI((fb & ~bzm) != 0)) return 0;
         if (UNI(fb != 0)) {
           bdirty = true;
-          ZW_SEARCH_DONE();
-          return run_bulk(IntC<0>{}, rb0, rb1, rb2, rb3, bid, d0, d1, d2, d3, fb, R, kb + k);
+          st.search_ends();
+          return zw_run_bulk<STRICT>(S, st, rb0, rb1, rb2, rb3, bid, d0, d1, d2, d3, fb, R, kb + k);
         }
       }
       for (int c = (pb >= 0 ? pb : p0) + 1; c < nch; c++) {
@@ -1263,28 +1087,23 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         double x0 = S.wa[0][q], x1 = S.wa[1][q], x2 = S.wa[2][q], x3 = S.wa[3][q];
         const int32_t xid = S.wid[q];
         const uint64_t xzm = rfl_u64(S.zm[c]);
-#ifdef PVT_STAMPS
-        n_probe++;
-#endif
+        st.probe();
         uint64_t fm = __ballot(p < nwin && fit_res<STRICT>(fmin(fmin(x0 - d0, x1 - d1),
                                                                 fmin(x2 - d2, x3 - d3))));
         if (FF) fm &= xzm;
         if (!FF && UNI((fm & ~xzm) != 0)) return 0;
         if (UNI(fm != 0)) {
-          ZW_SEARCH_DONE();
-          const int got = run_bulk(IntC<0>{}, x0, x1, x2, x3, xid, d0, d1, d2, d3, fm, R, kb + k);
+          st.search_ends();
+          const int got = zw_run_bulk<STRICT>(S, st, x0, x1, x2, x3, xid, d0, d1, d2, d3, fm, R, kb + k);
           if (p < nwin) { S.wa[0][p] = x0; S.wa[1][p] = x1; S.wa[2][p] = x2; S.wa[3][p] = x3; }
           if (!KEYED && lane == 0) S.touch[c] = 1;
           return got;
         }
       }
-      ZW_SEARCH_DONE();
+      st.search_ends();
       return 0;
     };
-#undef ZW_SEARCH_DONE
-#ifdef PVT_STAMPS
-    st_batch += zstamp() - tb0;
-#endif
+    st.batch_part_ends();
     int k = carry;                           // (>= kn: a run covered the batch whole, nothing to walk)
     while (UNI(k < kn)) {
       // (wave-uniform state the compiler cannot prove uniform: keeps the loops below scalar)
@@ -1312,41 +1131,29 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           // a run of tasks with this demand: placed in one pass over the chunk (run_bulk)
           const int R = run_len(k);
           if (UNI(R >= ZW_RMIN)) {
-            const int c = run_bulk(IntC<1>{}, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, m0, R, kb + k);
+            const int c = zw_run_bulk<STRICT>(S, st, ra0, ra1, ra2, ra3, rid, d0, d1, d2, d3, m0, R, kb + k);
             k += c;
             done += c;
             dirty = true;
-#ifdef PVT_STAMPS
-            n_chunks += c;
-            n_bulk += c;
-            n_runs++;
-#endif
+            st.run_placed(c);
             continue;
           }
           const bool win = __builtin_amdgcn_inverse_ballot_w64(m0 & (0ull - m0));
           ra0 = win ? n0 : ra0; ra1 = win ? n1 : ra1; ra2 = win ? n2 : ra2; ra3 = win ? n3 : ra3;
           if (win) {
-            S.lg[kb + k][0] = n0; S.lg[kb + k][1] = n1; S.lg[kb + k][2] = n2; S.lg[kb + k][3] = n3;
-            S.lgid[kb + k] = rid;
+            zw_log_entry(S, kb + k, rid, n0, n1, n2, n3);
           }
           dirty = true;
-#ifdef PVT_STAMPS
-          n_chunks++;
-          n_single++;
-#endif
+          st.single_placed();
           done++;
           k++;
         }
         if (UNI(k >= kn)) break;
         const int got = run_step(k);
+        st.run_placed(got);                    // (0: none, not counted)
         if (UNI(got > 0)) {
           k += got;
           done += got;
-#ifdef PVT_STAMPS
-          n_chunks += got;
-          n_bulk += got;
-          n_runs++;
-#endif
           continue;
         }
       }
@@ -1374,9 +1181,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         cur = a;
         uni = __ballot(lane >= k && lane < kn && tanc != cur) == 0;   // the rest of the batch
         __builtin_amdgcn_s_waitcnt(0xc07f);
-#ifdef PVT_STAMPS
-        n_switch++;
-#endif
+        st.anchor_switched();
       }
       // exact scores for this lane's host when it fits but is not zero-cost for `a`
       auto zero_exact = [&](bool f, bool k0, double a0, double a1, double a2, double a3, int q) {
@@ -1399,9 +1204,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       // (keyed first-fit: strict fit, a > d iff a - d > 0)
       const uint64_t fm0 = __ballot(fit_res<STRICT>(fmin(fmin(n0, n1), fmin(n2, n3)))) & rvalid;
       bool found = true;
-#ifdef PVT_STAMPS
-      n_chunks++;
-#endif
+      st.chunk_scanned();
       // Each path commits in place (no shared commit block: merging the paths made the compiler
       // copy the chunk registers on every task). commit: resc[h] -= t_demand
       // (cost_aware.py:95) on the lowest such lane, which logs.
@@ -1412,8 +1215,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         const bool win = __builtin_amdgcn_inverse_ballot_w64(m0 & (0ull - m0));
         ra0 = win ? n0 : ra0; ra1 = win ? n1 : ra1; ra2 = win ? n2 : ra2; ra3 = win ? n3 : ra3;
         if (win) {
-          S.lg[kb + k][0] = n0; S.lg[kb + k][1] = n1; S.lg[kb + k][2] = n2; S.lg[kb + k][3] = n3;
-          S.lgid[kb + k] = rid;
+          zw_log_entry(S, kb + k, rid, n0, n1, n2, n3);
         }
         dirty = true;
       } else {
@@ -1428,8 +1230,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
             const bool win = __builtin_amdgcn_inverse_ballot_w64(mb & (0ull - mb));
             rb0 = win ? q0 : rb0; rb1 = win ? q1 : rb1; rb2 = win ? q2 : rb2; rb3 = win ? q3 : rb3;
             if (win) {
-              S.lg[kb + k][0] = q0; S.lg[kb + k][1] = q1; S.lg[kb + k][2] = q2; S.lg[kb + k][3] = q3;
-              S.lgid[kb + k] = bid;
+              zw_log_entry(S, kb + k, bid, q0, q1, q2, q3);
             }
             bdirty = true;
             inb = true;
@@ -1440,12 +1241,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           store_b();                           // it works on LDS from p0 + 1 on
           double g0 = n0, g1 = n1, g2 = n2, g3 = n3;
           uint64_t fm = fm0, m = fm0 & rzm;
-#ifdef PVT_STAMPS
-          for (int pass = 0;; pass++) {        // the register chunk (advancing past dead ones)
-            n_chunks += pass > 0;
-#else
           for (;;) {                           // the register chunk (advancing past dead ones)
-#endif
             if (fm & ~rzm)                     // fitting hosts of U outside the anchor's
               m = __ballot(zero_exact((fm >> lane) & 1ull, (rzm >> lane) & 1ull, ra0, ra1, ra2,
                                       ra3, min(p0 * 64 + lane, nwin - 1))) & fm;   // zero-cost zones
@@ -1453,8 +1249,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
               const bool win = lane == __builtin_ctzll(m);
               ra0 = win ? g0 : ra0; ra1 = win ? g1 : ra1; ra2 = win ? g2 : ra2; ra3 = win ? g3 : ra3;
               if (win) {
-                S.lg[kb + k][0] = g0; S.lg[kb + k][1] = g1; S.lg[kb + k][2] = g2; S.lg[kb + k][3] = g3;
-                S.lgid[kb + k] = rid;
+                zw_log_entry(S, kb + k, rid, g0, g1, g2, g3);
               }
               dirty = true;
               found = true;
@@ -1469,13 +1264,12 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
             g0 = ra0 - d0; g1 = ra1 - d1; g2 = ra2 - d2; g3 = ra3 - d3;
             fm = __ballot(fit_res<STRICT>(fmin(fmin(g0, g1), fmin(g2, g3)))) & rvalid;
             m = fm & rzm;
+            st.chunk_scanned();
           }
           if (!found && p0 < nch) {
             store_chunk(p0);
             for (int c = p0 + 1; c < nch; c++) {
-#ifdef PVT_STAMPS
-              n_chunks++;
-#endif
+              st.chunk_scanned();
               const int p = c * 64 + lane;
               const int q = min(p, nwin - 1);
               const double a0 = S.wa[0][q], a1 = S.wa[1][q], a2 = S.wa[2][q], a3 = S.wa[3][q];
@@ -1488,8 +1282,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
                 if (lane == __builtin_ctzll(mc)) {
                   const double c0 = a0 - d0, c1 = a1 - d1, c2 = a2 - d2, c3 = a3 - d3;
                   S.wa[0][q] = c0; S.wa[1][q] = c1; S.wa[2][q] = c2; S.wa[3][q] = c3;
-                  S.lg[kb + k][0] = c0; S.lg[kb + k][1] = c1; S.lg[kb + k][2] = c2; S.lg[kb + k][3] = c3;
-                  S.lgid[kb + k] = id;
+                  zw_log_entry(S, kb + k, id, c0, c1, c2, c3);
                   if (!KEYED) S.touch[c] = 1;
                 }
                 found = true;
@@ -1509,17 +1302,13 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       done++;
       k++;
     }
-#ifdef PVT_STAMPS
-    tb0 = zstamp();
-#endif
+    st.batch_part_begins();
     fk = __builtin_amdgcn_readfirstlane(min(k, kn));
     fkb = kb;
     ftw = tw;
     fcal = tcal;
     carry = __builtin_amdgcn_readfirstlane(k > kn ? k - kn : 0);
-#ifdef PVT_STAMPS
-    st_batch += zstamp() - tb0;
-#endif
+    st.batch_part_ends();
   }
   flush_log();                               // the last batch walked
   if (KEYED) {   // the window's capacities to global availability: the keyed path goes on there
@@ -1554,45 +1343,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   // status[0]: tasks proven (their log entries are exact; validation accepts them), status[1]:
   // 1 when a certificate failed there (the rest of the chain is left to the list walk)
   if (lane == 0) report(done, (failed && !KEYED) ? (exhausted ? 2 : 1) : 0);
-#ifdef PVT_STAMPS
-  if (lane == 0 && A.stamps) {
-    const uint64_t t_end = zstamp();
-    atomicAdd((unsigned long long*)&A.stamps[0], (unsigned long long)(t_walk - t_start));
-    atomicAdd((unsigned long long*)&A.stamps[1], (unsigned long long)(t_end - t_walk));
-    atomicAdd((unsigned long long*)&A.stamps[2], (unsigned long long)n_chunks);
-    atomicAdd((unsigned long long*)&A.stamps[3], (unsigned long long)done);
-    atomicAdd((unsigned long long*)&A.stamps[4], (unsigned long long)n_switch);
-    atomicAdd((unsigned long long*)&A.stamps[5], (unsigned long long)n_bulk);
-    atomicAdd((unsigned long long*)&A.stamps[6], (unsigned long long)n_runs);
-    atomicAdd((unsigned long long*)&A.stamps[7], (unsigned long long)st_search);
-    atomicAdd((unsigned long long*)&A.stamps[8], (unsigned long long)st_p1);
-    atomicAdd((unsigned long long*)&A.stamps[9], (unsigned long long)st_p2);
-    atomicAdd((unsigned long long*)&A.stamps[10], (unsigned long long)n_probe);
-    atomicAdd((unsigned long long*)&A.stamps[11], (unsigned long long)n_iter);
-    atomicAdd((unsigned long long*)&A.stamps[12], (unsigned long long)st_batch);
-    atomicAdd((unsigned long long*)&A.stamps[13], (unsigned long long)n_single);
-    atomicAdd((unsigned long long*)&A.stamps[14], (unsigned long long)n_part);
-    atomicAdd((unsigned long long*)&A.stamps[15], (unsigned long long)s_pasg);
-    atomicAdd((unsigned long long*)&A.stamps[30], (unsigned long long)n_fromc);
-    atomicAdd((unsigned long long*)&A.stamps[31], (unsigned long long)n_rep);
-    atomicAdd((unsigned long long*)&A.stamps[20], (unsigned long long)(t_cert - t_start));
-    atomicAdd((unsigned long long*)&A.stamps[21], (unsigned long long)(t_win - t_cert));
-    atomicAdd((unsigned long long*)&A.stamps[22], (unsigned long long)(t_cap - t_win));
-    atomicAdd((unsigned long long*)&A.stamps[23], (unsigned long long)(t_walk - t_cap));
-    atomicAdd((unsigned long long*)&A.stamps[24], (unsigned long long)st_setup);
-    atomicAdd((unsigned long long*)&A.stamps[25], (unsigned long long)st_loop);
-    atomicAdd((unsigned long long*)&A.stamps[26], (unsigned long long)st_who);
-    atomicAdd((unsigned long long*)&A.stamps[27], (unsigned long long)st_rep);
-    atomicAdd((unsigned long long*)&A.stamps[28], (unsigned long long)n_cf);
-    atomicAdd((unsigned long long*)&A.stamps[29], (unsigned long long)(t_load - t_start));
-    if (b < ZW_STAMP_CHAINS) {
-      uint64_t* pc = A.stamps + ZW_STAMP_CHAIN + 8 * b;
-      const uint64_t v[8] = {n_calls, n_cont, st_between, st_cont, t_end - t_walk, (uint64_t)done,
-                             (uint64_t)nt, 0};
-      for (int q = 0; q < 8; q++) atomicAdd((unsigned long long*)&pc[q], (unsigned long long)v[q]);
-    }
-  }
-#endif
+  if (lane == 0) st.add_to(A.stamps, b, done, nt);
 }
 
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st) {

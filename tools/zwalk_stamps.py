@@ -61,7 +61,6 @@ print("    pass 2: snapshot choice + host ids %.0f, replay %.0f cycles per call 
       % (buf[26] / max(buf[6], 1), buf[27] / max(buf[6], 1), buf[31] / max(buf[6], 1), buf[27] / max(buf[31], 1)))
 print("    calls with a partial lane: %d of %d, mean asg %.1f; calls that replayed a lane from the start: %d"
       % (buf[14], buf[6], buf[15] / max(buf[14], 1), buf[30]))
-print("    runs counted in closed form: %d of %d" % (buf[28], buf[6]))
 print("  batches    %10.0f cycles per task (records, run masks, log flush)" % (buf[12] / max(buf[3], 1)))
 print("  single     %10d tasks on the one-task hot path" % buf[13])
 # per chain: run_bulk calls; those that continued a run a cap had cut (the task before the call's
