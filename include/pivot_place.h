@@ -428,6 +428,65 @@ typedef struct pvt_meter_log {
 int  pvt_meter(pvt_ctx* ctx, const pvt_meter_log* m);
 
 /*
+ * Meter usage series of a batch of S scenarios: the reference's series, Meter.plot_host_usage
+ * (resources/meter.py:135-148; Meter.save writes it to host_usage.json on every run, :128-133,
+ * alibaba/runner.py:46), Meter.plot_resource_usage (:150-159) and the five get_avg_*_usage
+ * (:161-179). With s = sample_size, bucket b is the time range [b*s, (b+1)*s).
+ *
+ * Inputs: hosts and intervals exactly as in pvt_meter_log; host h's usage records
+ * us_off[h] .. us_off[h+1] in time order (Meter.__usage, one record per resource at every host
+ * check-in / check-out, :181-187): us_time[u] and the four fractions us_frac[r * n_us + u],
+ * r = 0 cpus, 1 mem, 2 disk, 3 gpus. us_off, us_time and us_frac all NULL with n_us = 0: no
+ * resource series (res_hosts, res_mean and avg[1..4] are then not written). The caller sizes the
+ * output rows: scenario s owns buckets bucket_off[s] .. bucket_off[s+1] (nb_s of them) of the
+ * dense outputs, bucket_off[0] = 0, bucket_off[S] = n_buckets.
+ *
+ * Outputs, per scenario and bucket b < nb_s (every entry of a row is written):
+ *   n_hosts[bucket_off[s] + b]   hosts with an interval [start, end] that has
+ *                                start // s <= b <= end // s - 1: the bucket that holds `end` is
+ *                                not counted and an interval inside one bucket counts nowhere
+ *                                (:139-145). 0 = a bucket the reference's series leaves out.
+ *   res_hosts[bucket_off[s] + b] hosts with a record in b (time // s == b); 0 = left out.
+ *   res_mean[r * n_buckets + bucket_off[s] + b]   mean over those hosts of the mean of the
+ *                                host's values of resource r in b (:155-156); 0 when left out.
+ *   avg[s * 5 + k]               mean over the buckets not left out of n_hosts (k = 0) and of
+ *                                res_mean of resource k - 1 (k = 1..4); NaN without such a bucket.
+ * The integer outputs and avg[.. + 0] are exact; the means sum in another order than numpy
+ * (fp64, within 1e-9 relative; every term is non-negative). No floating-point atomics: a call's
+ * result does not depend on scheduling or on the other scenarios of the batch.
+ *
+ * Contract (PVT_EINVAL on a violation, with the number of violating scenarios in
+ * pvt_last_error; output contents are then unspecified): offsets in range and non-decreasing;
+ * every time finite with 0 <= t < 2^52; per host end >= start and start[i+1] >= end[i] (the
+ * meter's own order, :59-81) and us_time non-decreasing; the bucket of every interval start,
+ * interval end and record time lies below nb_s. 1 <= sample_size <= 2^31 - 1 (integral: then
+ * floor(floor(t) / s) in int64 is Python's float t // s). All pointers are device pointers.
+ * Synchronises before returning.
+ */
+typedef struct pvt_usage_log {
+  int32_t n_scen;             /* S                                                        */
+  int32_t reserved;           /* must be 0                                                */
+  int64_t sample_size;        /* s                                                        */
+  int64_t n_host_rows;        /* hosts of all scenarios                                   */
+  int64_t n_iv;               /* intervals of all hosts                                   */
+  int64_t n_us;               /* usage records of all hosts                               */
+  int64_t n_buckets;          /* buckets of all scenarios                                 */
+  const int64_t* host_off;    /* [S+1]                                                    */
+  const int64_t* iv_off;      /* [n_host_rows+1]                                          */
+  const double* iv_start;     /* [n_iv]                                                   */
+  const double* iv_end;       /* [n_iv]                                                   */
+  const int64_t* us_off;      /* [n_host_rows+1] or NULL                                  */
+  const double* us_time;      /* [n_us]                                                   */
+  const double* us_frac;      /* [4 * n_us]                                               */
+  const int64_t* bucket_off;  /* [S+1]                                                    */
+  int32_t* n_hosts;           /* [n_buckets] out                                          */
+  int32_t* res_hosts;         /* [n_buckets] out                                          */
+  double* res_mean;           /* [4 * n_buckets] out                                      */
+  double* avg;                /* [5 * S] out                                              */
+} pvt_usage_log;
+int  pvt_meter_usage(pvt_ctx* ctx, const pvt_usage_log* u);
+
+/*
  * Opt-in validation of a round's CONTENTS (no reference counterpart). The placement entry points
  * validate sizes, the mode and NULL pointers only and trust what the arrays hold -- zone, group
  * and anchor values index tables directly, and the kernels order keys by their bits -- so a caller

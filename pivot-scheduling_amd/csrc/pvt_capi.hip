@@ -1,6 +1,6 @@
 // pvt_capi.hip — the C ABI (include/pivot_place.h): context, scratch, profiling, round checks and
-// the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter (pvt_driver.h lists the
-// driver's other files).
+// the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter / pvt_meter_usage
+// (pvt_driver.h lists the driver's other files).
 //
 // pvt_place() replaces the body of a reference policy's schedule() (scheduler/__init__.py:79-80,
 // called at :103). A round runs as:
@@ -19,6 +19,7 @@
 #include "pvt_anchor.h"
 #include "pvt_groups.h"
 #include "pvt_meter.h"
+#include "pvt_usage.h"
 
 int pvt::fail(pvt_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -564,6 +565,40 @@ extern "C" int pvt_meter(pvt_ctx* ctx, const pvt_meter_log* m) {
   HIPCHK(hipMemcpyAsync(&nbad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (nbad) return fail(ctx, PVT_EINVAL, "%d scenario(s) with out-of-range meter offsets", nbad);
+  return PVT_OK;
+}
+
+// ---------------------------------------------------------------- meter usage series
+extern "C" int pvt_meter_usage(pvt_ctx* ctx, const pvt_usage_log* u) {
+  if (!ctx || !u) return PVT_EINVAL;
+  if (u->n_scen < 0 || u->reserved != 0 || u->n_host_rows < 0 || u->n_iv < 0 || u->n_us < 0 ||
+      u->n_buckets < 0 || u->sample_size < 1 || u->sample_size > INT32_MAX)
+    return fail(ctx, PVT_EINVAL, "bad size in pvt_usage_log");
+  if (u->n_scen == 0) return PVT_OK;
+  const bool has_us = u->us_off || u->us_time || u->us_frac;
+  if (!u->host_off || !u->iv_off || !u->bucket_off || !u->avg ||
+      (u->n_iv && (!u->iv_start || !u->iv_end)) || (u->n_buckets && !u->n_hosts) ||
+      (!u->us_off && (has_us || u->n_us)) || (u->n_us && (!u->us_time || !u->us_frac)) ||
+      (has_us && u->n_buckets && (!u->res_hosts || !u->res_mean)))
+    return fail(ctx, PVT_EINVAL, "null pointer in pvt_usage_log");
+  (void)hipSetDevice(ctx->device);
+  ENSURE(ctx->anc_scr, 16);
+  int32_t* bad = P<int32_t>(ctx->anc_scr);
+  HIPCHK(hipMemsetAsync(bad, 0, sizeof(int32_t), ctx->stream));
+  UsageArgs k{u->n_scen, u->sample_size, u->n_host_rows, u->n_iv, u->n_us, u->n_buckets,
+              u->host_off, u->iv_off, u->us_off, u->bucket_off,
+              u->iv_start, u->iv_end, u->us_time, u->us_frac,
+              u->n_hosts, u->res_hosts, u->res_mean, u->avg, bad};
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0,
+             16.0 * (double)u->n_iv + 40.0 * (double)u->n_us + 44.0 * (double)u->n_buckets);
+    launch_usage(k, ctx->stream);
+  }
+  HIPCHK(hipGetLastError());
+  int32_t nbad = 0;
+  HIPCHK(hipMemcpyAsync(&nbad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (nbad) return fail(ctx, PVT_EINVAL, "%d scenario(s) violating the usage log contract", nbad);
   return PVT_OK;
 }
 

@@ -97,6 +97,20 @@ class pvt_meter_log(ctypes.Structure):
                                        "congestion_delay")]
 
 
+class pvt_usage_log(ctypes.Structure):
+    _fields_ = [("n_scen", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (n, ctypes.c_int64) for n in ("sample_size", "n_host_rows", "n_iv", "n_us",
+                                      "n_buckets")] + [
+        (n, ctypes.c_void_p) for n in ("host_off", "iv_off", "iv_start", "iv_end", "us_off",
+                                       "us_time", "us_frac", "bucket_off", "n_hosts",
+                                       "res_hosts", "res_mean", "avg")]
+
+
+# pvt_usage_log: resource rows of us_frac / res_mean and columns 1..4 of avg (column 0: hosts)
+USAGE_RESOURCES = ("cpus", "mem", "disk", "gpus")
+USAGE_MAX_SAMPLE = 2 ** 31 - 1
+
+
 class pvt_ca_items(ctypes.Structure):
     _fields_ = [
         ("n_items", ctypes.c_int32),

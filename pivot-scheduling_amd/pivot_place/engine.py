@@ -73,6 +73,7 @@ def load_library(path=None):
         "pvt_set_resident": ([c_void_p, ctypes.c_int32], c_int),
         "pvt_anchor": ([c_void_p, c_void_p], c_int),
         "pvt_meter": ([c_void_p, c_void_p], c_int),
+        "pvt_meter_usage": ([c_void_p, c_void_p], c_int),
         "pvt_check_round": ([c_void_p, c_void_p, ctypes.POINTER(_abi.pvt_check_report)], c_int),
         "pvt_check_batch": ([c_void_p, c_void_p, ctypes.c_int32,
                              ctypes.POINTER(_abi.pvt_check_report)], c_int),
@@ -724,6 +725,34 @@ class PlacementEngine:
         self._set_stream(stream.cuda_stream)
         self._check(self.lib.pvt_meter(self.ctx, ctypes.addressof(m)))
         return {k: v[:S].cpu().numpy() for k, v in out.items()}
+
+    # -- meter usage series (pvt_meter_usage; reference resources/meter.py:135-179)
+    def meter_usage(self, log):
+        """Usage series of every scenario of a ``pivot_place.meter.UsageLog`` in one launch:
+        dict of numpy arrays ``bucket_off`` [S+1], ``n_hosts`` [NB] int32, ``res_hosts`` [NB]
+        int32, ``res_mean`` [4, NB] and ``avg`` [S, 5] float64 (NB = bucket_off[S]). Without
+        usage records ``res_hosts`` / ``res_mean`` are zero and ``avg[:, 1:]`` is NaN."""
+        torch = _torch()
+        dev = self.device
+        keep = {name: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+                for name, a in log.arrays() if a is not None}
+        S, NB = log.n_scen, int(log.bucket_off[-1])
+        out = {"n_hosts": torch.zeros(max(NB, 1), dtype=torch.int32, device=dev),
+               "res_hosts": torch.zeros(max(NB, 1), dtype=torch.int32, device=dev),
+               "res_mean": torch.zeros(4 * max(NB, 1), dtype=torch.float64, device=dev),
+               "avg": torch.full((5 * max(S, 1),), float("nan"), dtype=torch.float64,
+                                 device=dev)}
+        m = log.fill(lambda a: None, [o.data_ptr() for o in out.values()])
+        for name, t in keep.items():
+            setattr(m, name, t.data_ptr() if t.numel() else None)
+        stream = torch.cuda.current_stream(dev)
+        self._set_stream(stream.cuda_stream)
+        self._check(self.lib.pvt_meter_usage(self.ctx, ctypes.addressof(m)))
+        return {"bucket_off": log.bucket_off.copy(),
+                "n_hosts": out["n_hosts"][:NB].cpu().numpy(),
+                "res_hosts": out["res_hosts"][:NB].cpu().numpy(),
+                "res_mean": out["res_mean"][:4 * NB].cpu().numpy().reshape(4, NB),
+                "avg": out["avg"][:5 * S].cpu().numpy().reshape(S, 5)}
 
     # -- host-dimension sharding (include/pivot_place.h, pvt_shard_*); see pivot_place.sharded
     def shard_begin(self, dr: DeviceRound, host_lo, host_hi, world):
