@@ -39,9 +39,14 @@ extern "C" {
 
 /* Zones of a round: 1 <= pvt_round.n_zones <= PVT_MAX_ZONES at every entry point that takes a
  * round; more is PVT_EINVAL and nothing is written. Up to 32 zones a round runs the fast paths
- * (zone tables in LDS, zero-cost frontier walks, group epochs, one-wave resident walks); from 33
- * on the same policies run bit-exactly on the list-based windows and the wide resident kernels,
- * which read the Z x Z tables from global memory. pvt_max_zones() is the loaded library's bound. */
+ * (zone tables in LDS, zero-cost frontier walks, group epochs, one-wave resident walks). From 33
+ * on, the windowed engine runs the group epochs and the frontier walks for unsharded cost_aware
+ * rounds without rt_bw whose zero-cost components have at most 32 zones each (a chain of a larger
+ * component, and any chain a certificate fails for, goes to the lists); every other wide round
+ * -- host-sharded, rt_bw, the resident kernels -- runs bit-exactly on the list-based windows and
+ * the wide resident kernels, which read the Z x Z tables from global memory and run no one-wave
+ * walk. PVT_ZW_WIDE=0 at pvt_ctx_create keeps all wide rounds on the lists. pvt_max_zones() is
+ * the loaded library's bound. */
 #define PVT_MAX_ZONES 512
 
 /* Return codes. */
@@ -202,6 +207,9 @@ int  pvt_set_pipeline(pvt_ctx* ctx, int on);
  * and walked again in the next epoch, if a host an earlier group committed to is its winner or
  * beats it); results are identical either way. Replaces the group loop of
  * scheduler/cost_aware.py:37-42 around _best_fit (:63-97).
+ * Rounds of 33 to PVT_MAX_ZONES zones plan epochs when they are unsharded and have no rt_bw
+ * (host-sharded and rt_bw wide rounds, and every wide round under PVT_ZW_WIDE=0, take the
+ * pipelined list windows).
  * pvt_epoch_stats: epochs run, segments walked and segments rejected in the last pvt_place.
  */
 int  pvt_set_epochs(pvt_ctx* ctx, int on);
@@ -211,7 +219,10 @@ int  pvt_epoch_stats(pvt_ctx* ctx, int64_t* epochs, int64_t* segments, int64_t* 
  * tasks all find a zero-egress-cost host (score exactly 0) among the first 1024 hosts of its
  * zones is walked as a first fit over those hosts in LDS, with no candidate lists; the walk
  * proves each winner exact (pvt_zwalk.hip) and leaves any chain it cannot prove to the
- * list-based walk. pvt_zero_walk_stats: chains of the last pvt_place walked each way, and the
+ * list-based walk. In a round of 33 to PVT_MAX_ZONES zones (unsharded, no rt_bw) a chain is
+ * walked when its anchors' zero-cost component has at most 32 zones; chains of larger
+ * components, host-sharded and rt_bw wide rounds and the resident kernels' one-wave walks are
+ * not (PVT_ZW_WIDE=0 at pvt_ctx_create: no wide round is). pvt_zero_walk_stats: chains of the last pvt_place walked each way, and the
  * tasks of each epoch's longest chain (summed over its epochs: the walks' critical path).
  */
 int  pvt_set_zero_walk(pvt_ctx* ctx, int on);

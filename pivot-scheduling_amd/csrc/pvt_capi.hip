@@ -162,6 +162,7 @@ extern "C" int pvt_ctx_create(int device, pvt_ctx** out) {
   if (const char* e = getenv("PVT_EPOCH_TAIL")) ctx->t_epoch_tail = atoi(e) != 0;      // A/B
   if (const char* e = getenv("PVT_CHAIN_CERT")) ctx->t_chain_cert = atoi(e) != 0;      // A/B
   if (const char* e = getenv("PVT_ZW_RUNREM")) ctx->t_zw_runrem = atoi(e) != 0;        // A/B
+  if (const char* e = getenv("PVT_ZW_WIDE")) ctx->t_zw_wide = atoi(e) != 0;            // A/B
   if (const char* e = getenv("PVT_MERGE_SMALL")) ctx->t_merge_bitonic = atoi(e) == 0;  // A/B
   if (const char* e = getenv("PVT_RES_WAVES")) ctx->res_waves = atoi(e) == 8 ? 8 : atoi(e) == 2 ? 2 : atoi(e) == 1 ? 1 : 4;  // A/B
   *out = ctx;
@@ -182,7 +183,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->ksorttmp, &ctx->kflag, &ctx->ep_dev, &ctx->wres, &ctx->hmin, &ctx->cmax, &ctx->fwin,
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
-                 &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
+                 &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->zpairs, &ctx->zcomp, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
                  &ctx->chk_owner};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);

@@ -133,6 +133,10 @@ struct RoundState {
   bool gathered = false;          // ... and group_sort_gather_kernel wrote the gathered order
   bool prep_fused = false;        // build_order's order_scatter_kernel filled placement / zone tables
   int ffe_skip = -1;              //   the group they could not start (the keyed path takes it)
+  // rounds of more than ZMAX zones: frontier-walked epochs that missed (WIDE_MISS_MAX of them
+  // hand the rest of the round to the list windows), and that hand-over from place_epochs at t0
+  int wide_misses = 0;
+  bool ep_to_lists = false;
   // vbp best-fit band lists (pvt_band.hip): the sorted snapshot of hosts [lo, hi) is built; a
   // walk whose committed hosts are not yet flagged as touched (its own-ids buffer)
   bool band = false;
@@ -196,6 +200,7 @@ struct pvt_ctx {
   int t_epoch_tail = 1;           // PVT_EPOCH_TAIL: 0 = every frontier-walked epoch runs the tail kernels
   int t_chain_cert = 1;           // PVT_CHAIN_CERT: 0 = every frontier walk scans its chain's demand rows
   int t_zw_runrem = 1;            // PVT_ZW_RUNREM: 0 = the walk finds its runs itself, 64 tasks at the most
+  int t_zw_wide = 1;              // PVT_ZW_WIDE: 0 = rounds of more than ZMAX zones plan no epoch and no frontier walk
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
   int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
   int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
@@ -211,6 +216,9 @@ struct pvt_ctx {
   Buf zundo;                      // frontier walks' optimistic apply: per chain, what undoes it (ZwUndo)
   Buf gcert;                      // the grouped order's group certificates (GroupCert per group)
   Buf run_rem;                    //   and its run lengths (GatherOut.run_rem, int32 per gathered task)
+  Buf zpairs, zcomp;              // rounds of more than ZMAX zones: the sum table's zero pairs
+                                  //   (launch_zero_pairs), zone -> component root (ZwalkArgs.zcomp)
+  std::vector<int32_t> zpairs_host;
   int32_t* ep_host = nullptr;     // pinned staging of ep_dev
   int32_t* ep_hdev = nullptr;     // ep_host's device address (the accept kernel's readback)
   pvt_round* rstage = nullptr;    // pvt_place_batch: descriptors staged for the device (pinned)
@@ -243,6 +251,20 @@ struct pvt_ctx {
   std::vector<CheckRound> chk_host;          // the rounds as the check reads them (uploaded)
   Buf chk_desc, chk_slots, chk_rep, chk_owner;
 };
+
+// A round of more than ZMAX zones takes the group epochs and the frontier walks (the wide
+// instances, pvt_zwalk_wide.hip) when it is unsharded and has no realtime bandwidth; PVT_ZW_WIDE=0
+// keeps every such round on the list path.
+// A wide round whose zero-cost hosts run out gains nothing from epochs: every chain stops, and
+// each missed epoch scores a short list window with the wide score pass, whose cost hardly
+// depends on the window's length (measured, DESIGN.md §2.6: 5.7x slower than the pipelined
+// windows at 512 zones). So after WIDE_MISS_MAX frontier-walked epochs that left a chain unproven
+// (first-fit: that accepted no group) the rest of the round takes the pipelined list windows.
+static constexpr int WIDE_MISS_MAX = 2;
+static inline bool wide_fast(const pvt_ctx* ctx) {
+  const RoundState& R = ctx->rs;
+  return ctx->t_zw_wide && !R.sharded && R.world <= 1 && !R.r.rt_bw;
+}
 
 // Functions shared between the driver files: hidden, so the library exports the C ABI only.
 #pragma GCC visibility push(hidden)

@@ -365,6 +365,9 @@ struct ZwalkArgs {
   int32_t* hcert;
   ChainTab tab;           // chain mode: the epoch's chain tables by value (tab.nch > 0), or none
   ChainCert cert;         // chain mode: cert.fast = the fast prologue (launch_zwalk), or none
+  // chain mode, rounds of more than ZMAX zones (launch_zwalk_wide): zone -> the root of its
+  // zero-cost component [Z] (the driver's zero_cost_components), else NULL
+  const int32_t* zcomp;
 };
 constexpr int ZW_CERT_FAST = 1 << 8;
 // PVT_STAMPS builds: chain b's own words in the stamps buffer, 8 from ZW_STAMP_CHAIN + 8 b (past
@@ -382,6 +385,16 @@ void launch_zwalk_big(const ZwalkArgs& a, int nchains, hipStream_t st);
 // cost_aware first-fit with sort_hosts: the zero-key chain walk (FF mode; hmin = the
 // launch_host_absmax partials)
 void launch_zwalk_ff(const ZwalkArgs& a, int nchains, hipStream_t st);
+// Rounds of more than ZMAX zones (pvt_zwalk_wide.hip; a.zcomp set): the same chain walks on the
+// zones of the chain's zero-cost component, renumbered 0..k-1 in ascending zone id (k <= ZMAX;
+// a chain of a larger component reports (0, 1): the list walk takes it). big: the ZW_MBIG window.
+void launch_zwalk_wide(const ZwalkArgs& a, int nchains, bool big, hipStream_t st);
+void launch_zwalk_ff_wide(const ZwalkArgs& a, int nchains, hipStream_t st);
+// The zone pairs a < z with csum[a][z] == 0.0 of a Z x Z sum table, as words a << 16 | z in
+// pairs[1 ..] in any order, their count in pairs[0] (zeroed here; pairs past cap are counted and
+// not stored).
+constexpr int ZP_MAX = 8191;
+void launch_zero_pairs(const double* csum, int Z, int32_t* pairs, int cap, hipStream_t st);
 void launch_host_absmax(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);
 constexpr int ZW_M = 1024;                 // frontier-walk window hosts
 constexpr int ZW_MBIG = 3072;              // the large window (a retry for chains that outgrow ZW_M)

@@ -426,14 +426,17 @@ int pvt::round_begin(pvt_ctx* ctx, const pvt_round* rin, int lo, int hi, int wor
   // minima: written by the grouped order's launch, or queued below, they are ready while the
   // host waits for the grouped order's counts
   const bool want_hmin = ctx->epochs && ctx->zwalk && r->mode == PVT_CA_BF && r->task_group &&
-                         r->n_groups >= 2 && T >= 2 && !r->rt_bw && Z <= ZMAX && world == 1;
+                         r->n_groups >= 2 && T >= 2 && !r->rt_bw && (Z <= ZMAX || wide_fast(ctx)) &&
+                         world == 1;
+  // (rounds of more than ZMAX zones: the minima only -- no prebuilt windows, no group certificates)
+  const bool want_zwin = want_hmin && ctx->t_zpre && Z <= ZMAX;
   if (want_hmin) {
     ENSURE(ctx->hmin, sizeof(double) * 4 * ZW_MIN_PARTS);
-    if (ctx->t_zpre) ENSURE(ctx->zwin, sizeof(ZoneWindows));
+    if (want_zwin) ENSURE(ctx->zwin, sizeof(ZoneWindows));
   }
   bool hmin_done = false;
   if ((rc = build_order(ctx, r, &R.ord, &pending, want_hmin ? P<double>(ctx->hmin) : nullptr,
-                        &hmin_done, want_hmin && ctx->t_zpre ? P<ZoneWindows>(ctx->zwin) : nullptr)))
+                        &hmin_done, want_zwin ? P<ZoneWindows>(ctx->zwin) : nullptr)))
     return rc;
   if (!R.prep_fused) HIPCHK(hipMemsetAsync(r->placement, 0xff, sizeof(int32_t) * T, st));
   auto order_out = [&]() -> int {   // (the gather also writes the caller's order)
@@ -559,7 +562,9 @@ int pvt::round_begin(pvt_ctx* ctx, const pvt_round* rin, int lo, int hi, int wor
   // keyed first-fit: zero-key epochs (ff_epoch) over the groups, unsharded rounds
   R.ffe = false;
   R.ffe_skip = -1;
-  if (R.keyed && !R.sharded && ctx->zwalk && ctx->epochs && !r->rt_bw && Z <= ZMAX &&
+  R.wide_misses = 0;
+  R.ep_to_lists = false;
+  if (R.keyed && !R.sharded && ctx->zwalk && ctx->epochs && !r->rt_bw && (Z <= ZMAX || wide_fast(ctx)) &&
       T >= KEYED_FRONTIER_MIN) {
     R.egs = R.gstart;
     R.ega = R.ganchor;
@@ -667,6 +672,7 @@ ZwalkArgs pvt::zwalk_chain_args(pvt_ctx* ctx, int t0) {
   a.coff = dev + EP_COFF; a.cmap = dev + EP_CMAP; a.csoff = dev + EP_CSOFF; a.cseg = dev + EP_CSEG;
   a.status = dev + EP_STATUS;
   a.hmin = P<double>(ctx->hmin);
+  if (ctx->rs.Z > ZMAX) a.zcomp = P<int32_t>(ctx->zcomp);   // (the wide walk's components)
   return a;
 }
 
@@ -768,6 +774,8 @@ int pvt::round_next_window(pvt_ctx* ctx, int* nt_out) {
     if ((rc = ff_epoch(ctx, &adv))) return rc;
     if (adv > 0) { R.t0 += adv; continue; }
     R.ffe_skip = (int)R.g;          // (this group goes to the keyed path below)
+    // (a wide round whose zero-key epochs keep accepting nothing plans no more of them)
+    if (R.Z > ZMAX && ++R.wide_misses >= WIDE_MISS_MAX) R.ffe = false;
   }
   if (R.kstall) {                 // same group, frozen keys: complete the order
     R.kstall = false;
@@ -1147,6 +1155,7 @@ int pvt::place_windowed(pvt_ctx* ctx, const pvt_round* r) {
   ctx->n_zchains = ctx->n_gchains = ctx->n_longest = ctx->n_fastpro = 0;
   if ((rc = epoch_groups(ctx))) return rc;
   rc = (ctx->rs.egs.empty() || ctx->rs.ffe) ? place_pipelined(ctx) : place_epochs(ctx);
+  if (!rc && ctx->rs.ep_to_lists) rc = place_pipelined(ctx);   // (a wide round handed over, from R.t0)
   ctx->rs.active = false;
   if (rc) {
     (void)hipStreamSynchronize(ctx->side);

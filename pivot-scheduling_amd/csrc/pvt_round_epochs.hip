@@ -7,10 +7,68 @@
 // Zones joined by zero egress cost (csum = 0) form one component: a group's winners are the
 // lowest-index fitting hosts of its anchor's component (score 0), so two groups anchored in one
 // component compete for the same hosts and an epoch never holds both (R.ecomp: zone -> root).
+//
+// Rounds of more than ZMAX zones (wide_components): the Z x Z table (2 MB at 512 zones) neither
+// crosses the bus nor is looped over. A launch over the device sum table lists the pairs a < z
+// with csum[a][z] == 0.0 -- the same doubles and the same test as below, fl(x + y) = fl(y + x) --
+// and the host unions those: what it copies and loops over is proportional to the zero pairs
+// (4 KB first, the rest only when there are more than ZP_FIRST - 1 of them). More than ZP_MAX
+// pairs: the table path below. The components go to the device for the wide walk (ctx->zcomp).
+static constexpr int ZP_FIRST = 1024;           // words of the first copy: the count and 1023 pairs
+static int wide_components(pvt_ctx* ctx, bool* done) {
+  RoundState& R = ctx->rs;
+  const int Z = R.Z;
+  hipStream_t st = ctx->stream;
+  *done = false;
+  ENSURE(ctx->zpairs, sizeof(int32_t) * (ZP_MAX + 1));
+  std::vector<int32_t>& hp = ctx->zpairs_host;
+  hp.resize(ZP_MAX + 1);
+  launch_zero_pairs(P<double>(ctx->csum), Z, P<int32_t>(ctx->zpairs), ZP_MAX, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(hp.data(), ctx->zpairs.p, sizeof(int32_t) * ZP_FIRST, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int n = hp[0];
+  if (n < 0 || n > ZP_MAX) return PVT_OK;       // (too many: the caller takes the table)
+  if (n + 1 > ZP_FIRST) {
+    HIPCHK(hipMemcpyAsync(hp.data() + ZP_FIRST, P<int32_t>(ctx->zpairs) + ZP_FIRST,
+                          sizeof(int32_t) * (size_t)(n + 1 - ZP_FIRST), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  R.ecomp.resize(Z);
+  R.ezcomp.resize(Z);
+  for (int z = 0; z < Z; z++) R.ecomp[z] = R.ezcomp[z] = z;
+  auto zroot = [&](int z) { while (R.ezcomp[z] != z) z = R.ezcomp[z] = R.ezcomp[R.ezcomp[z]]; return z; };
+  for (int i = 1; i <= n; i++) {
+    const int a = hp[i] >> 16, z = hp[i] & 0xffff;
+    if (a < 0 || a >= Z || z >= Z) return fail(ctx, PVT_EHIP, "zero pair (%d, %d) of %d zones", a, z, Z);
+    R.ezcomp[zroot(a)] = zroot(z);
+  }
+  for (int z = 0; z < Z; z++) R.ezcomp[z] = zroot(z);
+  if (ctx->t_epoch_plan) R.ecomp = R.ezcomp;    // (PVT_EPOCH_PLAN=0: distinct zones only)
+  *done = true;
+  return PVT_OK;
+}
+
+// The components to the device, for the wide frontier walk (ZwalkArgs.zcomp).
+static int upload_components(pvt_ctx* ctx) {
+  const RoundState& R = ctx->rs;
+  static_assert(sizeof(int) == sizeof(int32_t), "zone components as int32");
+  ENSURE(ctx->zcomp, sizeof(int32_t) * (size_t)R.Z);
+  HIPCHK(hipMemcpyAsync(ctx->zcomp.p, R.ezcomp.data(), sizeof(int32_t) * (size_t)R.Z, hipMemcpyHostToDevice,
+                        ctx->stream));
+  return PVT_OK;
+}
+
 int pvt::zero_cost_components(pvt_ctx* ctx) {
   RoundState& R = ctx->rs;
   const pvt_round* r = &R.r;
   const int Z = R.Z;
+  if (Z > ZMAX) {
+    bool done = false;
+    int rc = wide_components(ctx, &done);
+    if (rc) return rc;
+    if (done) return upload_components(ctx);
+  }
   std::vector<double> cost((size_t)Z * Z);
   if (R.ginfo && R.cost_host.size() == cost.size()) {
     cost = R.cost_host;
@@ -35,7 +93,7 @@ int pvt::zero_cost_components(pvt_ctx* ctx) {
     for (int z = 0; z < Z; z++)
       if (cost[(size_t)a * Z + z] + cost[(size_t)z * Z + a] == 0.0) R.ezcomp[zroot(a)] = zroot(z);
   for (int z = 0; z < Z; z++) R.ezcomp[z] = zroot(z);
-  return PVT_OK;
+  return Z > ZMAX ? upload_components(ctx) : PVT_OK;
 }
 
 // cost_aware best-fit rounds of several groups (pvt_epoch.hip). The groups in processing
@@ -48,7 +106,9 @@ int pvt::epoch_groups(pvt_ctx* ctx) {
   R.ega.clear();
   const int T = R.T;
   if (!ctx->epochs || r->mode != PVT_CA_BF || !r->task_group || r->n_groups < 2 || T < 2) return PVT_OK;
-  if (R.Z > ZMAX) return PVT_OK;              // wide rounds: pipelined windows (32-bit zone masks here)
+  // rounds of more than ZMAX zones: epochs where the wide frontier walk can run (unsharded, no
+  // realtime bandwidth; PVT_ZW_WIDE=0: never), else pipelined windows as ever
+  if (R.Z > ZMAX && !wide_fast(ctx)) return PVT_OK;
   hipStream_t st = ctx->stream;
   int rc;
   std::vector<int> cnt(r->n_groups, 0);
@@ -223,10 +283,10 @@ static bool chain_cert(pvt_ctx* ctx, int t0, const EpochPlan& E, ChainCert& cc, 
 // A frontier-walked epoch whose chains all walk to their end needs none of the kernels after the
 // walk: each chain writes its window back itself (ZwalkArgs.undo: the optimistic
 // apply) and the host reads the verdict from the chains' own words. Where the walk owns its
-// window: unsharded rounds of at most ZMAX zones without realtime bandwidth.
+// window: unsharded rounds without realtime bandwidth (of more than ZMAX zones: the wide walk's).
 static bool tail_eligible(pvt_ctx* ctx) {
   const RoundState& R = ctx->rs;
-  return ctx->t_epoch_tail && !R.sharded && R.world <= 1 && !R.r.rt_bw && R.Z <= ZMAX;
+  return ctx->t_epoch_tail && !R.sharded && R.world <= 1 && !R.r.rt_bw && (R.Z <= ZMAX || wide_fast(ctx));
 }
 
 // Condition 2: no two chains hold anchors of one zero-cost component. A chain's zones U (its
@@ -235,21 +295,19 @@ static bool tail_eligible(pvt_ctx* ctx) {
 // write-back touches no host another chain reads or commits to. False under PVT_EPOCH_PLAN=0
 // whenever two chains' U intersect.
 static bool tail_chains_apart(const RoundState& R, int t0, const EpochPlan& E) {
-  if ((int)R.ezcomp.size() != R.Z || R.Z > ZMAX) return false;
+  if ((int)R.ezcomp.size() != R.Z) return false;
   size_t g = 0;
   while (g + 1 < R.egs.size() && R.egs[g + 1] <= t0) g++;
   const int nseg = (int)E.chain.size(), nch = (int)E.segs.size();
   if (nch > 64) return false;
-  std::vector<uint32_t> comps(nch, 0u);
+  std::vector<int> owner(R.Z, -1);           // component root -> the chain that holds its anchors
   for (int k = 0; k < nseg; k++, g++) {      // (segment k is the epoch's k-th group, epoch_plan)
     if (g >= R.ega.size()) return false;
     const int z = R.ega[g];
-    if (z >= 0 && z < R.Z) comps[E.chain[k]] |= 1u << R.ezcomp[z];   // (else: the walk bails)
-  }
-  uint32_t seen = 0;
-  for (int c = 0; c < nch; c++) {
-    if (seen & comps[c]) return false;
-    seen |= comps[c];
+    if (z < 0 || z >= R.Z) continue;         // (the walk bails)
+    int& o = owner[R.ezcomp[z]];
+    if (o >= 0 && o != E.chain[k]) return false;
+    o = E.chain[k];
   }
   return true;
 }
@@ -362,7 +420,8 @@ int pvt::ff_epoch(pvt_ctx* ctx, int* adv_out) {
   if (opt && (rc = tail_walk_args(ctx, za))) return rc;
   {
     Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
-    launch_zwalk_ff(za, nch, st);
+    if (R.Z > ZMAX) launch_zwalk_ff_wide(za, nch, st);
+    else launch_zwalk_ff(za, nch, st);
   }
   ctx->n_epochs++;
   ctx->n_segs += nseg;
@@ -434,8 +493,16 @@ int pvt::place_epochs(pvt_ctx* ctx) {
   int big_t0 = -1;                //   (at most once per epoch start)
   R.in_epoch = true;
   struct Reset { bool& f; ~Reset() { f = false; } } reset_{R.in_epoch};
-  const bool zw_possible = ctx->zwalk && !r->rt_bw && R.Z <= ZMAX;
+  const bool zones_ok = R.Z <= ZMAX || wide_fast(ctx);   // (the wide walk, pvt_zwalk_wide.hip)
+  const bool zw_possible = ctx->zwalk && !r->rt_bw && zones_ok;
   while (t0 < R.T) {
+    // (a wide round whose frontier walks keep missing: the rest on the pipelined list windows,
+    // from the state the accepted epochs left -- every accepted segment is applied by here)
+    if (R.Z > ZMAX && R.wide_misses >= WIDE_MISS_MAX) {
+      R.t0 = t0;
+      R.ep_to_lists = true;
+      return PVT_OK;
+    }
     // the frontier walk's host minima (certificate 2) depend only on the epoch's start state:
     // reduced while the host plans the epoch
     if (zw_possible && !force_lists && !(R.hmin_pre && t0 == 0)) {
@@ -450,7 +517,7 @@ int pvt::place_epochs(pvt_ctx* ctx) {
     ctx->n_segs += nseg;
     // chains the zero-cost frontier walk can prove need no candidate lists (pvt_zwalk.hip);
     // the lists are scored only for the others
-    const bool zw = ctx->zwalk && nch > 1 && !r->rt_bw && R.Z <= ZMAX && !force_lists;
+    const bool zw = ctx->zwalk && nch > 1 && !r->rt_bw && zones_ok && !force_lists;
     force_lists = false;
     if (!zw && (rc = window_lists(ctx, t0, nt, 0, st))) return rc;
     if (nch == 1) {                           // one chain: the plain walk (writes avail)
@@ -509,7 +576,8 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       if (fastp && !opt) za.hcert = dev + EP_CERT;
       {
         Scope sc(ctx, PVT_K_COMMIT, 0, 0, nullptr, "zwalk_kernel");
-        if (big) launch_zwalk_big(za, nch, st);
+        if (R.Z > ZMAX) launch_zwalk_wide(za, nch, big, st);
+        else if (big) launch_zwalk_big(za, nch, st);
         else launch_zwalk(za, nch, st);
       }
       const bool was_big = big;
@@ -540,6 +608,7 @@ int pvt::place_epochs(pvt_ctx* ctx) {
       int adv = 0;
       if ((rc = epoch_frontier_verdict(ctx, E, t0, &need, &adv))) return rc;
       if (need && adv < nt) {
+        R.wide_misses++;
         bool exhausted = false;
         for (int c = 0; c < nch; c++) exhausted |= host[EP_STATUS + 2 * c + 1] == 2;
         if (exhausted && !was_big && big_t0 != t0 + adv) {

@@ -115,6 +115,19 @@ __device__ __forceinline__ double wave_nmax_d(double v) {
   return wave_reduce_d(v, [](double a, double b) { return nan_max(a, b); });
 }
 
+// The wide instance's own LDS (rounds of more than ZMAX zones, pvt_zwalk_wide.hip): the zones of
+// the chain's zero-cost component renumbered 0..k-1 in ascending zone id. After the prologue the
+// walk runs on local ids alone (S.csum / S.bsum hold the component's k x k block, anchors and
+// window zones are local), exactly as a round of k zones.
+struct ZwWideLDS {
+  uint8_t zl[ZWIDE];                       // zone -> local id, ZL_NONE: not in the component
+  int16_t gl[ZMAX];                        // local id -> zone
+  int32_t seg[2 * ZW_WAVES];               // component zones per (pass, wave) of the numbering
+  int32_t root;                            // the component (its root in ZwalkArgs.zcomp), < 0: none
+  uint32_t aset;                           // the chain's anchors (local ids)
+};
+
+#ifndef PVT_ZWALK_WIDE_TU
 // Per-dimension minimum capacity over hosts [lo, hi) (certificate 2), ZW_MINB partials.
 __global__ __launch_bounds__(256) void host_min_kernel(const double* avail, int H, int lo, int hi,
                                                        double* part) {
@@ -136,6 +149,7 @@ __global__ __launch_bounds__(256) void host_min_kernel(const double* avail, int 
     part[blockIdx.x * 4 + tid] = v;
   }
 }
+#endif
 
 // A compile-time integer as a function argument (run_bulk: the dimensions a run updates).
 template <int N> struct IntC { static constexpr int value = N; };
@@ -347,11 +361,22 @@ __device__ __forceinline__ int zw_run_bulk(ZwalkLDS<WM>& S, ZwStamps& st, double
 // alive hosts (the driver's ordered_frontier), same mechanics.
 // FAST: the fast prologue of the round's first best-fit epoch (below), a template flag so that
 // neither instance carries both prologues.
-template <bool KEYED, bool STRICT, bool FF = false, int WM = ZW_M, bool FAST = false>
+// WMP: the window's hosts; negative for the WIDE instance of that window (rounds of more than ZMAX
+// zones, instantiated in pvt_zwalk_wide.hip): chain mode, the ordinary prologue, and in it the
+// chain's component renumbered (ZwWideLDS); everything wide is discarded from the other instances.
+template <bool KEYED, bool STRICT, bool FF = false, int WMP = ZW_M, bool FAST = false>
 __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
+  constexpr bool WIDE = WMP < 0;
+  constexpr int WM = WIDE ? -WMP : WMP;
   static_assert(!FF || (!KEYED && STRICT), "FF: chain mode, strict fit");
   static_assert(WM == ZW_M || !KEYED, "keyed / ordered / sharded windows: ZW_M hosts");
+  static_assert(!WIDE || (!KEYED && !FAST), "wide: chain mode, the ordinary prologue");
   __shared__ ZwalkLDS<WM> S;
+  [[maybe_unused]] ZwWideLDS* W = nullptr;
+  if constexpr (WIDE) {
+    __shared__ ZwWideLDS wide_lds;
+    W = &wide_lds;
+  }
   ZwStamps st;
   st.start();
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -368,7 +393,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   const int32_t* gcmap = KEYED ? nullptr : A.cmap + base;
   const bool segm = !KEYED && (tabm || A.cseg);   // group segment starts break runs
   int32_t* status = A.status + 2 * b;
-  const int Z = A.Z, H = A.H;
+  // (WIDE: Z becomes the zones of the chain's component in the prologue; ZG stays the round's)
+  int Z = A.Z;
+  const int H = A.H;
+  [[maybe_unused]] const int ZG = A.Z;
   // the chain's report (one thread): the device words the epoch kernels read and, with the
   // optimistic apply, the host's mapped words -- no later kernel copies them
   auto report = [&](int s0, int s1) {
@@ -561,7 +589,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     // tables, the host minima, the chain's first task positions, its segment range), so the
     // prologue waits for about two HBM latencies, not one per step.
     static_assert(ZMAX * ZMAX <= 4 * ZW_THREADS && ZW_MINB == ZW_THREADS, "prologue loads");
-    const int ZZ = KEYED ? 0 : Z * Z;
+    const int ZZ = (KEYED || WIDE) ? 0 : Z * Z;   // (WIDE: the component's block, gathered below)
     double cs[4], bs[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -604,7 +632,22 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     const int sg0 = tabm ? A.tab.csoff[b] : (!KEYED && A.cseg) ? A.csoff[b] : 0;
     const int sg1 = tabm ? A.tab.csoff[b + 1] : (!KEYED && A.cseg) ? A.csoff[b + 1] : 0;
     // prebuilt windows' zone sets (ZoneWindows; lane j: zone j's, 0 = none)
-    const uint32_t zpu = (!KEYED && WM == ZW_M && A.zpre && lane < Z) ? A.zpre->U[lane] : 0u;
+    const uint32_t zpu = (!KEYED && !WIDE && WM == ZW_M && A.zpre && lane < Z) ? A.zpre->U[lane] : 0u;
+    // WIDE: the zones' components (two zones per thread), and the chain's component from its
+    // first task's anchor
+    static_assert(ZWIDE == 2 * ZW_THREADS, "wide prologue: two zones per thread");
+    [[maybe_unused]] int zc0 = -1, zc1 = -1;
+    if constexpr (WIDE) {
+      zc0 = tid < ZG ? A.zcomp[tid] : -1;
+      zc1 = tid + ZW_THREADS < ZG ? A.zcomp[tid + ZW_THREADS] : -1;
+      W->zl[tid] = ZL_NONE;
+      W->zl[tid + ZW_THREADS] = ZL_NONE;
+      if (tid == 0) {
+        const int a0 = nt > 0 ? A.anc[max(wv[0], 0)] : -1;
+        W->root = (a0 >= 0 && a0 < ZG) ? A.zcomp[a0] : -2;
+        W->aset = 0;
+      }
+    }
 
 #pragma unroll
     for (int u = 0; u < 4; u++) {
@@ -616,6 +659,43 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (tid < WM / 64) S.touch[tid] = 0;
     st.loaded();
     __syncthreads();
+    if constexpr (WIDE) {
+      // The component's zones numbered in ascending zone id (pass p, thread t: zone 256 p + t; a
+      // ballot per wave, the waves' counts through LDS), the local -> zone list, and the
+      // component's k x k block of the sum tables gathered into S.csum / S.bsum: the same
+      // doubles the walk of a k-zone round would read. More than ZMAX zones: no walk.
+      const int root = W->root;
+      const bool m0 = root >= 0 && zc0 == root, m1 = root >= 0 && zc1 == root;
+      const uint64_t b0 = __ballot(m0), b1 = __ballot(m1);
+      if (lane == 0) { W->seg[wave] = __popcll(b0); W->seg[ZW_WAVES + wave] = __popcll(b1); }
+      __syncthreads();
+      int base0 = 0, base1 = 0, k = 0;
+#pragma unroll
+      for (int w = 0; w < 2 * ZW_WAVES; w++) {
+        const int c = W->seg[w];
+        base0 += w < wave ? c : 0;
+        base1 += w < ZW_WAVES + wave ? c : 0;
+        k += c;
+      }
+      const uint64_t below = (1ull << lane) - 1ull;
+      const int l0 = base0 + __popcll(b0 & below), l1 = base1 + __popcll(b1 & below);
+      if (m0 && l0 < ZMAX) { W->zl[tid] = (uint8_t)l0; W->gl[l0] = (int16_t)tid; }
+      if (m1 && l1 < ZMAX) { W->zl[tid + ZW_THREADS] = (uint8_t)l1; W->gl[l1] = (int16_t)(tid + ZW_THREADS); }
+      if (k < 1 || k > ZMAX) S.bail = 1;       // benign race: every writer stores 1
+      Z = min(k, ZMAX);
+      __syncthreads();
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        const int i = tid + u * ZW_THREADS;
+        if (i < Z * Z) {
+          const int la = i / Z, lz = i - la * Z;
+          const int g = (int)W->gl[la] * ZG + (int)W->gl[lz];
+          S.csum[i] = A.csum[g];
+          S.bsum[i] = A.bsum[g];
+        }
+      }
+      __syncthreads();
+    }
     if (!KEYED && tid < Z) {                   // anchor row -> zero-cost zone mask
       uint32_t m = 0;
       for (int z = 0; z < Z; z++) m |= (S.csum[tid * Z + z] == 0.0) ? (1u << z) : 0u;
@@ -663,7 +743,9 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
 #pragma unroll
         for (int r = 0; r < 4; r++) bm[r] = ok ? dv[u][r] : DINF;
         if (ok) {
-          const int a = av[u];
+          int a = av[u];
+          // (WIDE: the anchor's local id; a zone of another component is no anchor of this chain)
+          if constexpr (WIDE) a = (a >= 0 && a < ZG) ? (int)W->zl[a] : (int)ZL_NONE;
           if (a < 0 || a >= Z) {
             bad = true;
           } else {
@@ -705,7 +787,27 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     }
     if (bad) S.bail = 1;                        // benign race: every writer stores 1
     if (um) atomicOr(&S.umask, um);
+    if constexpr (WIDE) {
+      if (abits) atomicOr(&W->aset, abits);
+    }
     __syncthreads();
+    if constexpr (WIDE) {
+      // Certificate 2 / 2' for the zones outside the component, on every anchor row of the chain
+      // (coalesced along the row): c >= 2^-300 and 0 < bw <= 2^300, the clause the walk applies per
+      // anchor to the component's own zones outside U. Taken here over all of the chain's anchors
+      // at once: a failure leaves the whole chain to the exact path (stricter than the per-anchor
+      // test, never wrong). c != 0 there by the component's definition.
+      bool out_bad = false;
+      for (uint32_t m = W->aset; m; m &= m - 1) {
+        const int ga = W->gl[__builtin_ctz(m)];
+        for (int z = tid; z < ZG; z += ZW_THREADS) {
+          const double c = A.csum[ga * ZG + z], bw = A.bsum[ga * ZG + z];
+          if (W->zl[z] == ZL_NONE) out_bad |= !((c >= 0x1p-300) && (bw > 0.0) && (bw <= 0x1p300));
+        }
+      }
+      if (out_bad) S.bail = 1;
+      __syncthreads();
+    }
     st.certified();
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -742,7 +844,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       if (tid == 0) report(0, (KEYED || nt <= 0) ? 0 : 1);
       return;
     }
-    const FrontierSlot* pw = A.pwin ? A.pwin + (KEYED ? 0 : b) : nullptr;
+    const FrontierSlot* pw = (!WIDE && A.pwin) ? A.pwin + (KEYED ? 0 : b) : nullptr;   // (wide rounds: unsharded)
     // the round's first epoch: the window the grouped order's launch prebuilt for the component of
     // the chain's anchors (its zone set U' covers U; a window over U' is exact, with U' in the
     // certificates)
@@ -774,6 +876,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       for (int p = tid; p < nw; p += ZW_THREADS) { S.wid[p] = A.lo + A.kperm[p]; S.wz[p] = 0; }
       if (tid == 0) S.nwin = nw;
       __syncthreads();
+    } else if constexpr (WIDE) {               // window: U's hosts in index order, zones through
+      // the table (membership and S.wz by local id: a zone of another component never enters)
+      compact_zone_window_local_t<WM, ZW_THREADS, ZW_SCAN>(A.zone, ZoneLocal{ZG, W->zl, U}, 0, H, S.wid,
+                                                           S.wz, S.cnt, &S.nwin);
     } else {                                   // window: U's hosts in index order
       compact_zone_window<WM>(A.zone, Z, U, 0, H, S.wid, S.wz, S.cnt, &S.nwin);
     }
@@ -912,10 +1018,17 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   // b + 1's records and batch b + 2's chain positions are in flight (no HBM latency at a batch
   // start)
   auto task_at = [&](int i) { return i < nt ? (KEYED ? i : gcmap[i]) : 0; };
+  // a task's anchor (WIDE: its local id; the prologue checked every chain task's anchor, and a
+  // lane past the chain's end reads task 0's, which no test looks at)
+  auto anc_at = [&](int w) -> int {
+    const int a = A.anc[w];
+    if constexpr (WIDE) return W->zl[min((uint32_t)a, (uint32_t)(ZWIDE - 1))];
+    else return a;
+  };
   int nw = task_at(lane);
   double nd0 = A.dem[(size_t)nw * 4 + 0], nd1 = A.dem[(size_t)nw * 4 + 1];
   double nd2 = A.dem[(size_t)nw * 4 + 2], nd3 = A.dem[(size_t)nw * 4 + 3];
-  int nanc = A.anc[nw], ncal = A.ord[nw];
+  int nanc = anc_at(nw), ncal = A.ord[nw];
   // run lengths from the order launch (the fast prologue's instance, where the driver has them):
   // loaded with the batch's records
   const bool rrm = FAST && A.run_rem != nullptr;
@@ -981,7 +1094,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       nw = nw1;
       nd0 = A.dem[(size_t)nw * 4 + 0]; nd1 = A.dem[(size_t)nw * 4 + 1];
       nd2 = A.dem[(size_t)nw * 4 + 2]; nd3 = A.dem[(size_t)nw * 4 + 3];
-      nanc = A.anc[nw]; ncal = A.ord[nw];
+      nanc = anc_at(nw); ncal = A.ord[nw];
       if (rrm) nrr = A.run_rem[nw];
       nw1 = task_at(i0 + 128 + lane);
     }
@@ -1346,6 +1459,33 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
   if (lane == 0) st.add_to(A.stamps, b, done, nt);
 }
 
+#ifdef PVT_ZWALK_WIDE_TU
+// ---- rounds of more than ZMAX zones (this section alone is compiled into pvt_zwalk_wide.hip)
+void launch_zwalk_wide(const ZwalkArgs& a, int nchains, bool big, hipStream_t st) {
+  if (big) PVT_LAUNCH((zwalk_kernel<false, false, false, -ZW_MBIG>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
+  else PVT_LAUNCH((zwalk_kernel<false, false, false, -ZW_M>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
+}
+void launch_zwalk_ff_wide(const ZwalkArgs& a, int nchains, hipStream_t st) {
+  PVT_LAUNCH((zwalk_kernel<false, true, true, -ZW_M>), dim3(nchains), dim3(ZW_THREADS), 0, st, a);
+}
+
+// The zero pairs of the sum table (the driver's components of a wide round): block a scans row a
+// for z > a; a pair takes a slot from the counter in pairs[0].
+__global__ __launch_bounds__(256) void zero_pairs_kernel(const double* csum, int Z, int32_t* pairs,
+                                                         int cap) {
+  const int a = blockIdx.x;
+  for (int z = a + 1 + threadIdx.x; z < Z; z += 256) {
+    if (csum[a * Z + z] == 0.0) {
+      const int slot = atomicAdd(&pairs[0], 1);
+      if (slot < cap) pairs[1 + slot] = (a << 16) | z;
+    }
+  }
+}
+void launch_zero_pairs(const double* csum, int Z, int32_t* pairs, int cap, hipStream_t st) {
+  (void)hipMemsetAsync(pairs, 0, sizeof(int32_t), st);
+  PVT_LAUNCH(zero_pairs_kernel, dim3(Z), dim3(256), 0, st, csum, Z, pairs, cap);
+}
+#else
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st) {
   PVT_LAUNCH(host_min_kernel, dim3(ZW_MINB), dim3(256), 0, st, avail, H, lo, hi, part);
 }
@@ -1532,5 +1672,6 @@ void launch_zwin_merge(const uint8_t* pkgs, int64_t pkg_bytes, int world, int ns
   PVT_LAUNCH(zwin_merge_kernel, dim3(nslots + 1), dim3(256), 0, st, pkgs, pkg_bytes, world,
                      nslots, out, hmin);
 }
+#endif  // PVT_ZWALK_WIDE_TU
 
 }  // namespace pvt
