@@ -178,7 +178,8 @@ int  pvt_get_kstats(pvt_ctx* ctx, int kclass, pvt_kstats* out);
  * placement path ("zwalk_kernel", "commit_kernel", "lwalk_kernel", "opp_commit_kernel",
  * "opp_count_kernel", "score_kernel", "band_score_kernel", "perm_scan_kernel", "ordered_kernel",
  * "resident_kernel", "merge_kernel", "merge_small_kernel", "merge_pkg_kernel",
- * "merge_path_kernel"; and "check_kernel" of pvt_check_round / pvt_set_checks), each bracketed
+ * "merge_path_kernel"; "check_kernel" of pvt_check_round / pvt_set_checks; and
+ * "host_ops_kernel", the segment walk of pvt_host_ops_apply), each bracketed
  * by its own HIP events on the stream it runs on. An unknown or unlaunched name gives zeros. */
 int  pvt_get_kernel_kstats(pvt_ctx* ctx, const char* kernel, pvt_kstats* out);
 /* With profiling on = 2, record events around the launches of this one named kernel only
@@ -496,6 +497,48 @@ typedef struct pvt_usage_log {
   double* avg;                /* [5 * S] out                                              */
 } pvt_usage_log;
 int  pvt_meter_usage(pvt_ctx* ctx, const pvt_usage_log* u);
+
+/*
+ * Resident cluster state: a log of subscribe / unsubscribe ops applied to the hosts' levels on
+ * the device, by the rules of the reference's host accounting (HostResource.subscribe,
+ * resources/__init__.py:433-449, and HostResource.unsubscribe, :451-461, over SimPy containers;
+ * cpus_used etc. are `capacity - level`, :401-415). A caller that simulates many rounds keeps
+ * `level` on the device and sends the few thousand ops between two rounds instead of a new
+ * 4 x H snapshot.
+ *
+ * State: capacity[r * H + h] (constant) and level[r * H + h] (in/out), fp64, in the layout of
+ * pvt_round.avail, r = 0 cpus, 1 mem, 2 disk, 3 gpus. The log holds K ops in event order:
+ * op_host[k], op_kind[k] (0 subscribe, 1 unsubscribe) and the amounts d_r = op_amt[r * K + k].
+ * The ops of one host are applied in log order; ops of different hosts are independent.
+ *
+ *   subscribe(d)    refused if, for any r, d_r > level_r or d_r < 0 (:436-440): op_ok[k] = 0 and
+ *                   nothing changes. Otherwise level_r -= d_r for every r with d_r > 0
+ *                   (:441-448) and op_ok[k] = 1.
+ *   unsubscribe(d)  independently for each r: if 0 < d_r and d_r <= capacity_r - level_r (the
+ *                   subtraction rounded once, in fp64), then level_r += d_r (:454-461).
+ *                   op_ok[k] = the mask of the resources put back (bit r). A put-back that
+ *                   misses the test by an ulp is skipped, as in the reference.
+ *
+ * The compares are IEEE compares, so NaN, infinite and negative amounts behave as in Python (a
+ * NaN amount passes the subscribe test and changes nothing). One rounding per add or subtract,
+ * no contraction, no floating-point atomics: the result is bit-identical across calls and does
+ * not depend on how a log is cut into calls.
+ *
+ * PVT_EINVAL when an op names a host outside [0, H) or a kind other than 0 or 1; pvt_last_error
+ * names the first such op, and neither level nor op_ok is written. Runs on the context's stream
+ * and synchronises before returning; n_ops = 0 returns PVT_OK without a launch. All pointers
+ * are device pointers. Timed under the name "host_ops_kernel" (pvt_get_kernel_kstats).
+ */
+typedef struct pvt_host_ops {
+  int32_t n_hosts, n_ops;     /* H >= 1, K >= 0                                           */
+  const double* capacity;     /* [4 * H]                                                  */
+  double* level;              /* [4 * H] in/out                                           */
+  const int32_t* op_host;     /* [K]                                                      */
+  const int32_t* op_kind;     /* [K] 0 subscribe, 1 unsubscribe                           */
+  const double* op_amt;       /* [4 * K]                                                  */
+  int32_t* op_ok;             /* [K] out                                                  */
+} pvt_host_ops;
+int  pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* ops);
 
 /*
  * Opt-in validation of a round's CONTENTS (no reference counterpart). The placement entry points

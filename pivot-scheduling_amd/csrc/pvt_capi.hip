@@ -1,6 +1,6 @@
 // pvt_capi.hip — the C ABI (include/pivot_place.h): context, scratch, profiling, round checks and
-// the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter / pvt_meter_usage
-// (pvt_driver.h lists the driver's other files).
+// the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter / pvt_meter_usage /
+// pvt_host_ops_apply (pvt_driver.h lists the driver's other files).
 //
 // pvt_place() replaces the body of a reference policy's schedule() (scheduler/__init__.py:79-80,
 // called at :103). A round runs as:
@@ -20,6 +20,7 @@
 #include "pvt_groups.h"
 #include "pvt_meter.h"
 #include "pvt_usage.h"
+#include "pvt_hostops.h"
 
 int pvt::fail(pvt_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -184,7 +185,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
                  &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->zpairs, &ctx->zcomp, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
-                 &ctx->chk_owner};
+                 &ctx->chk_owner, &ctx->ho_key, &ctx->ho_idx, &ctx->ho_tmp, &ctx->ho_flag};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->evpool) (void)hipEventDestroy(e);
@@ -600,6 +601,46 @@ extern "C" int pvt_meter_usage(pvt_ctx* ctx, const pvt_usage_log* u) {
   HIPCHK(hipMemcpyAsync(&nbad, bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   if (nbad) return fail(ctx, PVT_EINVAL, "%d scenario(s) violating the usage log contract", nbad);
+  return PVT_OK;
+}
+
+// ---------------------------------------------------------------- resident host levels
+extern "C" int pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* o) {
+  if (!ctx || !o) return PVT_EINVAL;
+  if (o->n_hosts < 1 || o->n_ops < 0) return fail(ctx, PVT_EINVAL, "bad size in pvt_host_ops");
+  if (o->n_ops == 0) return PVT_OK;
+  if (!o->capacity || !o->level || !o->op_host || !o->op_kind || !o->op_amt || !o->op_ok)
+    return fail(ctx, PVT_EINVAL, "null pointer in pvt_host_ops");
+  (void)hipSetDevice(ctx->device);
+  const size_t K = (size_t)o->n_ops;
+  size_t tmp_bytes = 0;
+  HIPCHK(hostops_sort_temp(o->n_hosts, o->n_ops, &tmp_bytes));
+  ENSURE(ctx->ho_key, 2 * K * sizeof(uint32_t));
+  ENSURE(ctx->ho_idx, 2 * K * sizeof(int32_t));
+  ENSURE(ctx->ho_tmp, tmp_bytes);
+  ENSURE(ctx->ho_flag, 16);
+  uint32_t* bad = P<uint32_t>(ctx->ho_flag);
+  HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), ctx->stream));   // HO_NO_BAD
+  HostOpsArgs k{o->n_hosts, o->n_ops, o->capacity, o->level, o->op_host, o->op_kind, o->op_amt,
+                o->op_ok, P<uint32_t>(ctx->ho_key), P<uint32_t>(ctx->ho_key) + K,
+                P<int32_t>(ctx->ho_idx), P<int32_t>(ctx->ho_idx) + K, bad};
+  launch_hostops_keys(k, ctx->stream);
+  HIPCHK(hostops_sort(k, ctx->ho_tmp.p, tmp_bytes, ctx->stream));
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, 60.0 * (double)K, nullptr, "host_ops_kernel");
+    launch_hostops_apply(k, ctx->stream);
+  }
+  HIPCHK(hipGetLastError());
+  uint32_t first = HO_NO_BAD;
+  HIPCHK(hipMemcpyAsync(&first, bad, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (first != HO_NO_BAD) {
+    int32_t hk[2] = {0, 0};
+    HIPCHK(hipMemcpy(&hk[0], o->op_host + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&hk[1], o->op_kind + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(ctx, PVT_EINVAL, "op %u of the host op log: host %d (of %d), kind %d", first,
+                hk[0], o->n_hosts, hk[1]);
+  }
   return PVT_OK;
 }
 

@@ -250,6 +250,8 @@ struct pvt_ctx {
   int n_cus = 0;                  // the grid of the check kernel is sized from the CU count
   std::vector<CheckRound> chk_host;          // the rounds as the check reads them (uploaded)
   Buf chk_desc, chk_slots, chk_rep, chk_owner;
+  // pvt_host_ops_apply: (host, k) keys and op indices, in and sorted out, the sort's temp, flag
+  Buf ho_key, ho_idx, ho_tmp, ho_flag;
 };
 
 // A round of more than ZMAX zones takes the group epochs and the frontier walks (the wide

@@ -111,6 +111,16 @@ USAGE_RESOURCES = ("cpus", "mem", "disk", "gpus")
 USAGE_MAX_SAMPLE = 2 ** 31 - 1
 
 
+class pvt_host_ops(ctypes.Structure):
+    _fields_ = [("n_hosts", ctypes.c_int32), ("n_ops", ctypes.c_int32)] + [
+        (n, ctypes.c_void_p) for n in ("capacity", "level", "op_host", "op_kind", "op_amt",
+                                       "op_ok")]
+
+
+# pvt_host_ops.op_kind
+HOST_OP_SUBSCRIBE, HOST_OP_UNSUBSCRIBE = 0, 1
+
+
 class pvt_ca_items(ctypes.Structure):
     _fields_ = [
         ("n_items", ctypes.c_int32),

@@ -74,6 +74,7 @@ def load_library(path=None):
         "pvt_anchor": ([c_void_p, c_void_p], c_int),
         "pvt_meter": ([c_void_p, c_void_p], c_int),
         "pvt_meter_usage": ([c_void_p, c_void_p], c_int),
+        "pvt_host_ops_apply": ([c_void_p, c_void_p], c_int),
         "pvt_check_round": ([c_void_p, c_void_p, ctypes.POINTER(_abi.pvt_check_report)], c_int),
         "pvt_check_batch": ([c_void_p, c_void_p, ctypes.c_int32,
                              ctypes.POINTER(_abi.pvt_check_report)], c_int),
@@ -753,6 +754,45 @@ class PlacementEngine:
                 "res_hosts": out["res_hosts"][:NB].cpu().numpy(),
                 "res_mean": out["res_mean"][:4 * NB].cpu().numpy().reshape(4, NB),
                 "avg": out["avg"][:5 * S].cpu().numpy().reshape(S, 5)}
+
+    # -- resident host levels (pvt_host_ops_apply; reference resources/__init__.py:433-461)
+    def host_ops(self, capacity, level, op_host, op_kind, op_amt):
+        """Apply a subscribe / unsubscribe log to ``level`` in place, by the reference's rules
+        (``pivot_place.hostops.apply_ops`` states them in Python). Device tensors: ``capacity``
+        and ``level`` float64 with 4*H elements, ``op_host`` and ``op_kind`` int32 [K],
+        ``op_amt`` float64 with 4*K elements (resource-major). Returns ``op_ok``, a device int32
+        tensor [K]: 0 / 1 for a subscribe, the mask of the resources put back for an
+        unsubscribe. An invalid log raises and leaves ``level`` as it was."""
+        torch = _torch()
+        H, K = level.numel() // 4, op_host.numel()
+        for t, dt, n in ((capacity, torch.float64, 4 * H), (level, torch.float64, 4 * H),
+                         (op_host, torch.int32, K), (op_kind, torch.int32, K),
+                         (op_amt, torch.float64, 4 * K)):
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("host_ops: a contiguous device tensor of %s with %d elements "
+                                 "expected" % (dt, n))
+        op_ok = torch.empty(K, dtype=torch.int32, device=level.device)
+        self.host_ops_into(capacity, level, op_host, op_kind, op_amt, op_ok)
+        return op_ok
+
+    def host_ops_into(self, capacity, level, op_host, op_kind, op_amt, op_ok):
+        """``host_ops`` writing a caller's ``op_ok`` tensor (untouched by an invalid log)."""
+        o = _abi.pvt_host_ops()
+        o.n_hosts, o.n_ops = level.numel() // 4, op_host.numel()
+        o.capacity, o.level = capacity.data_ptr(), level.data_ptr()
+        o.op_host, o.op_kind = op_host.data_ptr(), op_kind.data_ptr()
+        o.op_amt, o.op_ok = op_amt.data_ptr(), op_ok.data_ptr()
+        self._bind_stream()
+        self._check(self.lib.pvt_host_ops_apply(self.ctx, ctypes.addressof(o)))
+
+    def restore_hosts(self, avail, avail0, hosts):
+        """``avail[:, h] = avail0[:, h]`` for every h of ``hosts`` (pvt_restore_hosts): device
+        float64 tensors with 4*H elements and a device int32 tensor; entries outside [0, H) and
+        duplicates are harmless."""
+        self._bind_stream()
+        self._check(self.lib.pvt_restore_hosts(self.ctx, avail.data_ptr(), avail0.data_ptr(),
+                                               avail.numel() // 4, hosts.data_ptr(),
+                                               hosts.numel()))
 
     # -- host-dimension sharding (include/pivot_place.h, pvt_shard_*); see pivot_place.sharded
     def shard_begin(self, dr: DeviceRound, host_lo, host_hi, world):
