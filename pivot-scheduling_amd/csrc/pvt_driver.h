@@ -85,6 +85,7 @@ struct RoundState {
   int kmode = 0;                  // 1: zero-key prefix in host order, 2: full sort
   int kn = 0;                     // hosts in the current order (prefix length in mode 1)
   bool kstall = false;            // a walk found a prefix list exhausted: sort the rest
+  int kstall_t0 = -1;             // the task of the last such stall (host-sharded: see walk_status)
   int32_t* ord = nullptr;         // processing order (ctx scratch)
   std::vector<int> gstart, ganchor, gid;   // keyed groups: starts, anchors, caller's group ids
   size_t g = 0, ngroups = 0;

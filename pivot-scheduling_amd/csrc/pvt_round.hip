@@ -479,7 +479,7 @@ int pvt::round_begin(pvt_ctx* ctx, const pvt_round* rin, int lo, int hi, int wor
   // group boundaries in processing order (only cost_aware first-fit with sort_hosts needs them)
   R.keyed = r->mode == PVT_CA_FF && r->sort_hosts;
   R.kscan = false;
-  R.kmode = 0; R.kn = 0; R.kstall = false;
+  R.kmode = 0; R.kn = 0; R.kstall = false; R.kstall_t0 = -1;
   R.ordered = (r->mode == PVT_VBP_FF) || (r->mode == PVT_CA_FF && !r->sort_hosts);
   if (R.keyed) {
     std::vector<int32_t> tg, ga;
@@ -1026,8 +1026,15 @@ int pvt::walk_status(pvt_ctx* ctx, int t0, int nt, bool inherited, int* adv) {
   if (*adv == -1) return fail(ctx, PVT_EHIP, "commit walk: ring hand-off timed out at task %d", t0);
   if (*adv < 0 || *adv > nt) return fail(ctx, PVT_EHIP, "commit walk returned %d of %d", *adv, nt);
   if (*adv == 0 && !inherited) {
-    if (ctx->rs.kscan && ctx->rs.kmode == 1) {   // a zero-key prefix ran dry: sort the rest
-      ctx->rs.kstall = true;
+    RoundState& R = ctx->rs;
+    // a zero-key prefix ran dry: sort the rest. Host-sharded, the prefix may be another rank's:
+    // each rank chooses prefix or full sort by the zero-key hosts of its own range, while the walk
+    // and its report are the same everywhere. A rank whose own order is complete (or that has no
+    // host) takes the same step, once per task, and scores the window again.
+    const bool others = R.sharded && R.world > 1 && R.kstall_t0 != t0;
+    if (R.kscan && (R.kmode == 1 || others)) {
+      R.kstall = true;
+      R.kstall_t0 = t0;
       return PVT_OK;
     }
     return fail(ctx, PVT_EHIP, "commit walk made no progress at task %d", t0);
