@@ -42,6 +42,7 @@
 #include "pvt_groups_dev.h"
 #include "pvt_kernels.h"
 #include "pvt_mt.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
@@ -50,29 +51,9 @@ constexpr int RES_CHUNK = 256;           // tasks whose demand rows are staged i
 constexpr int RES_MT_STRIDE = 628;       // words per wave-private MT19937 copy (625 used)
 constexpr uint64_t NONE = ~0ull;
 
-// Diagnostic phase stamps (PVT_STAMPS builds; tools/resident_stamps.py): block 0, wave 0 only.
-#ifdef PVT_STAMPS
-constexpr int RES_STAMP_BASE = 32, RES_STAMP_ROUNDS = 4096;   // per-round cycles (stamps build)
-__device__ __forceinline__ uint64_t rstamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define RSTAMP(k)                         \
-  do {                                    \
-    if (stw) {                            \
-      const uint64_t t_ = rstamp();       \
-      ph[k] += t_ - tl;                   \
-      tl = t_;                            \
-    }                                     \
-  } while (0)
-#define RCOUNT(k) do { if (stw) ph[k] += 1; } while (0)
-#else
-#define RSTAMP(k) do {} while (0)
-#define RCOUNT(k) do {} while (0)
-#endif
+// Diagnostic stamps (`make stamps`; tools/resident_stamps.py, fused_stamps.py): the phases and the
+// walk counters are block 0's (wave 0's, the walking wave's, thread 0's), the per-round cycle
+// words every workgroup's. The types and the slot map: pvt_stamps.h.
 
 // A run list entry: a host's full key (score bits, tiebreak:host) and its capacities.
 struct RunEntry {
@@ -305,10 +286,8 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
       wx[blk * 4 + tid - 64] = fmax(wx[blk * 4 + tid - 64], wx[(blk + 1) * 4 + tid - 64]);
   __syncthreads();
   if (wave == walker) {
-#ifdef PVT_STAMPS
-    uint64_t n_probe = 0, n_adv = 0, st_task = 0, n_bulk = 0, n_bulk_tasks = 0;
-    const uint64_t tw_start = rstamp();
-#endif
+    ResWalkStamps st;
+    st.walk_begins();
     const int nch = (H + 63) >> 6;
     int p0 = 0;
     double ra0, ra1, ra2, ra3;
@@ -439,9 +418,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
         E = __ballot(same);
       }
       for (int k = 0; k < kn; k++, p++) {
-#ifdef PVT_STAMPS
-        const uint64_t tk0 = rstamp();
-#endif
+        st.task_begins();
         p = __builtin_amdgcn_readfirstlane(p);
         p0 = __builtin_amdgcn_readfirstlane(p0);
         const double d0 = readlane_d(td[0], k), d1 = readlane_d(td[1], k);
@@ -492,15 +469,10 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
               if (lane >= s0 && lane < s1) who = id;
             }
             if (lane < covered) pl[p + lane] = who;
-#ifdef PVT_STAMPS
-            n_bulk++;
-            n_bulk_tasks += covered;
-#endif
+            st.run_placed(covered);
             k += covered - 1;                  // (the loop's increments add the last one)
             p += covered - 1;
-#ifdef PVT_STAMPS
-            st_task += rstamp() - tk0;
-#endif
+            st.task_ends();
             continue;
           }
         }
@@ -533,9 +505,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
             }
           } else {
             for (int c = dp0 + 1; c * 64 < nwin; c++) {
-#ifdef PVT_STAMPS
-              n_probe++;
-#endif
+              st.chunk_probed();
               const int i = c * 64 + lane;
               const bool v = i < nwin;
               const int32_t h = v ? wd[i] : 0;
@@ -594,9 +564,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
           while (zm == 0 && rk == 0 && p0 + 1 < nch &&
                  !__ballot(rv && fits<false>(ra0, ra1, ra2, ra3, mn0, mn1, mn2, mn3))) {
             store_chunk(p0);                   // dead: move the register chunk on
-#ifdef PVT_STAMPS
-            n_adv++;
-#endif
+            st.chunk_advanced();
             ++p0;
             load_chunk(p0);
             test(ra0, ra1, ra2, ra3, rz, rv, zm, rk);
@@ -613,9 +581,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
             win = -2;
           } else {
             for (int c = p0 + 1; c < nch; c++) {
-#ifdef PVT_STAMPS
-              n_probe++;
-#endif
+              st.chunk_probed();
               const int q = c * 64 + lane;
               const bool v = q < H;
               const int qq = v ? q : 0;
@@ -642,24 +608,13 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
         win = __builtin_amdgcn_readfirstlane(win);
         if (win == -2) { stop = true; break; }
         if (win >= 0 && lane == 0) pl[p] = win;
-#ifdef PVT_STAMPS
-        st_task += rstamp() - tk0;
-#endif
+        st.task_ends();
       }
     }
     leave_dense();
     store_chunk(p0);
     if (lane == 0) s_stop = p;
-#ifdef PVT_STAMPS
-    if (blockIdx.x == 0 && lane == 0 && A_stamps) {
-      A_stamps[10] += n_probe;
-      A_stamps[11] += n_adv;
-      A_stamps[13] += st_task;                  // cycles inside the task loop bodies
-      A_stamps[24] += n_bulk;                   // bulk runs and the tasks they placed
-      A_stamps[25] += n_bulk_tasks;
-      A_stamps[14] += rstamp() - tw_start;      // wave 0's whole walk (records included)
-    }
-#endif
+    st.walk_ends(A_stamps, lane);
   }
   __syncthreads();
   return s_stop;
@@ -705,10 +660,8 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
     for (int blk = nsb - 2; blk >= 0; blk--) ws[blk * 4 + tid] = fmin(ws[blk * 4 + tid], ws[(blk + 1) * 4 + tid]);
   __syncthreads();
   if (wave == walker) {
-#ifdef PVT_STAMPS
-    uint64_t n_probe = 0, n_adv = 0, st_task = 0, n_bulk = 0, n_bulk_tasks = 0;
-    const uint64_t tw_start = rstamp();
-#endif
+    ResWalkStamps st;
+    st.walk_begins();
     const int nch = (H + 63) >> 6;
     int p0 = 0;
     double ra0, ra1, ra2, ra3;
@@ -747,9 +700,7 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
         E = __ballot(same);
       }
       for (int k = 0; k < kn; k++, p++) {
-#ifdef PVT_STAMPS
-        const uint64_t tk0 = rstamp();
-#endif
+        st.task_begins();
         p = __builtin_amdgcn_readfirstlane(p);
         p0 = __builtin_amdgcn_readfirstlane(p0);
         const double d0 = readlane_d(td[0], k), d1 = readlane_d(td[1], k);
@@ -759,9 +710,7 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
         while (F == 0 && p0 + 1 < nch &&
                !__ballot(rv && fits<STRICT>(ra0, ra1, ra2, ra3, mn0, mn1, mn2, mn3))) {
           store_chunk(p0);
-#ifdef PVT_STAMPS
-          n_adv++;
-#endif
+          st.chunk_advanced();
           ++p0;
           load_chunk(p0);
           F = __ballot(rv && fits<STRICT>(ra0, ra1, ra2, ra3, d0, d1, d2, d3));
@@ -807,11 +756,8 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
               const int q = c * 64 + lane;
               wa[q] = y0; wa[RW_MAXH + q] = y1; wa[2 * RW_MAXH + q] = y2; wa[3 * RW_MAXH + q] = y3;
             }
-#ifdef PVT_STAMPS
-            n_bulk++;
-            n_bulk_tasks += covered;
-            st_task += rstamp() - tk0;
-#endif
+            st.run_placed(covered);
+            st.task_ends();
             k += covered - 1;
             p += covered - 1;
             continue;
@@ -824,9 +770,7 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
           win = p0 * 64 + w;
         } else {
           for (int c = p0 + 1; c < nch; c++) {
-#ifdef PVT_STAMPS
-            n_probe++;
-#endif
+            st.chunk_probed();
             const int q = c * 64 + lane;
             const bool v = q < H;
             const int qq = v ? q : 0;
@@ -844,23 +788,12 @@ __device__ int resident_walk_ff(const pvt_round& R, const ResLds& Lo, char* smem
           }
         }
         win = __builtin_amdgcn_readfirstlane(win);
+        st.task_ends();                         // (before the store: pvt_stamps.h on where a call may stand)
         if (win >= 0 && lane == 0) pl[p] = win;
-#ifdef PVT_STAMPS
-        st_task += rstamp() - tk0;
-#endif
       }
     }
     store_chunk(p0);
-#ifdef PVT_STAMPS
-    if (blockIdx.x == 0 && lane == 0 && A_stamps) {
-      A_stamps[10] += n_probe;
-      A_stamps[11] += n_adv;
-      A_stamps[13] += st_task;
-      A_stamps[14] += rstamp() - tw_start;
-      A_stamps[24] += n_bulk;
-      A_stamps[25] += n_bulk_tasks;
-    }
-#endif
+    st.walk_ends(A_stamps, lane);
   }
   __syncthreads();
   return T;
@@ -940,21 +873,15 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   // ca_bf 0.743 vs 0.779 ms at config 4); this path takes over where it stops, on the walked
   // capacities.
   int p_start = 0;
+  ResRoundStamps st;
   if (!WIDE && MODE == CA_BF && A.sw.walk_ca_bf && H <= RW_MAXH && T > 0 && !R.rt_bw) {
-#ifdef PVT_STAMPS
-    const uint64_t tw0 = rstamp();
-#endif
+    st.walk_called(A.stamps, tid);
     // the walking wave: 0, or (walk_rotate, A/B) one that moves with the workgroup index, so
     // two workgroups sharing a CU need not walk on the same SIMD
     const int walker = A.sw.walk_rotate ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
     p_start = resident_walk<NT>(R, Lo, smem, ord, pl, csum, bsum, has_groups, walker,
                                 A.sw.walk_bulk != 0, A.stamps);
-#ifdef PVT_STAMPS
-    if (blockIdx.x == 0 && tid == 0 && A.stamps) {   // walked tasks, walk cycles (block 0)
-      A.stamps[8] += (uint64_t)p_start;
-      A.stamps[9] += rstamp() - tw0;
-    }
-#endif
+    st.walk_returned(A.stamps, p_start);
     const double* wa = reinterpret_cast<const double*>(smem + Lo.wa);
 #pragma unroll
     for (int j = 0; j < HPL; j++) {
@@ -967,18 +894,11 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
   // first fit by index (vbp first-fit; cost_aware first-fit without sort_hosts): the whole round
   // walked by one wave (resident_walk_ff), this path then only writes the results
   if (!WIDE && (MODE == VBP_FF || (MODE == CA_FF && !keyed)) && A.sw.walk_ff && H <= RW_MAXH && T > 0) {
-#ifdef PVT_STAMPS
-    const uint64_t tw0 = rstamp();
-#endif
+    st.walk_called(A.stamps, tid);
     const int walker = A.sw.walk_rotate ? (int)(blockIdx.x % (unsigned)WAVES) : 0;
     p_start = resident_walk_ff<NT, MODE == CA_FF>(R, Lo, smem, ord, pl, walker, A.sw.walk_bulk != 0,
                                                   A.stamps);
-#ifdef PVT_STAMPS
-    if (blockIdx.x == 0 && tid == 0 && A.stamps) {
-      A.stamps[8] += (uint64_t)p_start;
-      A.stamps[9] += rstamp() - tw0;
-    }
-#endif
+    st.walk_returned(A.stamps, p_start);
     const double* wa = reinterpret_cast<const double*>(smem + Lo.wa);
 #pragma unroll
     for (int j = 0; j < HPL; j++) {
@@ -1005,13 +925,6 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
     __builtin_amdgcn_s_waitcnt(0xc07f);
   }
 
-#ifdef PVT_STAMPS
-  // phases: 0 anchor rows, 1 slot scan, 2 wave reduction, 3 exchange (post, barrier, merge),
-  // 4 full path, 5 commit; counts: 6 tasks, 7 full paths
-  const bool stw = blockIdx.x == 0 && wave == 0 && A.stamps != nullptr;
-  uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t tl = stw ? rstamp() : 0;
-#endif
   int cur_anc = -1, cur_grp = -1, cur_bgrp = -1;
   const bool rt = (MODE == CA_FF || MODE == CA_BF) && R.rt_bw != nullptr;
   // Sticky winner. A task whose demand is bit for bit the previous task's (same anchor, same
@@ -1131,6 +1044,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
     }
     return rem;
   };
+  st.round_begins(A.stamps, wave);
   for (int p0 = p_start; p0 < T; p0 += RES_CHUNK) {
     const int n = min(RES_CHUNK, T - p0);
     __syncthreads();                      // the previous chunk (and the sort keys) are consumed
@@ -1242,8 +1156,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           }
         }
       }
-      RSTAMP(0);
-      RCOUNT(6);
+      st.rows_loaded();
       if (MODE != OPP && sh >= 0) {
         // (sh >= 0 only when this task's demand, anchor and group equal the previous task's)
         const bool ok = fits<STRICT>(sc0, sc1, sc2, sc3, d0, d1, d2, d3);
@@ -1261,7 +1174,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
               dbits(n3) == dbits(d3) && (!CA || n_anc == anc_q) &&
               (!((MODE == CA_FF && keyed) || rt) || n_grp == grp_q);
           if (!same_next) sh = -1;
-          RSTAMP(5);
+          st.committed();
           continue;
         }
         sh = -1;
@@ -1344,12 +1257,12 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
             c = (f && (!keyed || ((zmask >> j) & 1u))) ? h0 + j : c;
           }
         }
-        RSTAMP(1);
+        st.scanned();
         const uint64_t any = __ballot(c != 0x7fffffff);
         int wc = any ? __builtin_amdgcn_readlane(c, __builtin_ctzll(any)) : 0x7fffffff;
         if (MODE == CA_BF && __ballot(risky)) wc = RISKY;   // (RISKY = -1: the signed minimum)
         int g = wc;
-        RSTAMP(2);
+        st.reduced();
         if (WAVES > 1) {
           if (lane == 0) fposts[par * RES_MAXW + wave] = wc;
           __syncthreads();
@@ -1361,7 +1274,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           g = v[0];
         }
         g = __builtin_amdgcn_readfirstlane(g);
-        RSTAMP(3);
+        st.exchanged();
         if (g >= 0 && g != 0x7fffffff) {
           hw = g;
           full = false;
@@ -1388,7 +1301,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           sb[j] = f ? dbits(norm2_seq(a0[j] - d0, a1[j] - d1, a2[j] - d2, a3[j] - d3)) : NONE;
           if (sb[j] < ls) { ls = sb[j]; lh = h0 + j; }
         }
-        RSTAMP(1);
+        st.scanned();
         const uint64_t m = wave_min_u64(ls);
         int wh = 0x7fffffff, near = 0;
         if (m != NONE) {
@@ -1402,7 +1315,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
         }
         uint64_t gm = m;
         int gh = wh, gnear = near;
-        RSTAMP(2);
+        st.reduced();
         if (WAVES > 1) {
           if (lane == 0) {
             vposts[(par * RES_MAXW + wave) * 2 + 0] = m;
@@ -1436,7 +1349,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           full = false;
           hw = __builtin_amdgcn_readfirstlane(gh);
         }
-        RSTAMP(3);
+        st.exchanged();
       }
       if (full) {
         // lane best: (score bits, tiebreak:host), first minimum in host order
@@ -1486,8 +1399,7 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           }
         }
         if (g2 != NONE) hw = __builtin_amdgcn_readfirstlane((int)(uint32_t)g2);
-        RCOUNT(7);
-        RSTAMP(4);
+        st.full_path_done();
       }
       if (hw == 0x7fffffff) continue;    // no host fits: the task stays waiting
       const int jw = hw & (HPL - 1);     // uniform: the owning lane's register slot
@@ -1558,13 +1470,10 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
           sh = -1;
         }
       }
-      RSTAMP(5);
+      st.committed();
     }
   }
-#ifdef PVT_STAMPS
-  if (stw && lane == 0)
-    for (int k = 0; k < 8; k++) A.stamps[k] += ph[k];
-#endif
+  st.round_ends(A.stamps, lane);
 
   __syncthreads();
   for (int i = tid; i < T; i += NT) G(R.placement)[ord[i]] = pl[i];
@@ -1589,15 +1498,10 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
 template <int MODE, int WAVES, int HPL>
 __global__ __launch_bounds__(WAVES * WAVE) void resident_kernel(ResidentArgs A) {
   const pvt_round R = reinterpret_cast<const pvt_round*>(A.rounds)[blockIdx.x];   // SGPRs
-#ifdef PVT_STAMPS
-  // per round (diagnostic): cycles of the whole workgroup, from its start to its end
-  const uint64_t t_round = rstamp();
-#endif
+  RoundCycles rc;
+  rc.begin();
   resident_round<MODE, WAVES, HPL>(A, R);
-#ifdef PVT_STAMPS
-  if (threadIdx.x == 0 && A.stamps && blockIdx.x < RES_STAMP_ROUNDS)
-    A.stamps[RES_STAMP_BASE + blockIdx.x] = rstamp() - t_round;
-#endif
+  rc.end(A.stamps);
 }
 
 // A batch of rounds of different policies in one launch (pvt_place_host_batch: the lock-step
@@ -1754,17 +1658,11 @@ __global__ __launch_bounds__(4 * WAVE) void resident_fused_kernel(FusedArgs F) {
   if (threadIdx.x < (int)(sizeof(pvt_round) / 8))
     reinterpret_cast<uint64_t*>(F.dev + fr.desc)[threadIdx.x] =
         reinterpret_cast<const uint64_t*>(F.hmap + fr.desc)[threadIdx.x];
-#ifdef PVT_STAMPS
-  // phases of block 0 (stamps[16..20]): stage in, anchors, grouping, placement, results out
-  const bool fst = blockIdx.x == 0 && threadIdx.x == 0 && F.ra.stamps;
-  uint64_t ft = fst ? rstamp() : 0;
-#define FSTAMP(k) do { if (fst) { const uint64_t t_ = rstamp(); F.ra.stamps[16 + (k)] += t_ - ft; ft = t_; } } while (0)
-#else
-#define FSTAMP(k) do {} while (0)
-#endif
+  FusedStamps st;
+  st.begins(F.ra.stamps);
   block_copy2<16>(F.dev, F.hmap, fr.out_lo, fr.out_hi - fr.out_lo, fr.in_lo, fr.in_hi - fr.in_lo);
   __syncthreads();
-  FSTAMP(0);
+  st.staged_in();
   if (ITEMS && fr.items >= 0) {
     const int wave = threadIdx.x >> 6;
     uint64_t* lds = reinterpret_cast<uint64_t*>(smem);
@@ -1775,19 +1673,18 @@ __global__ __launch_bounds__(4 * WAVE) void resident_fused_kernel(FusedArgs F) {
       block_item(a, a.deferred[q], lds, lds + ANC_LDS);
       __syncthreads();
     }
-    FSTAMP(1);
+    st.anchors_done();
     ca_groups_round<4 * WAVE, RES_MAX_TASKS>(g, *reinterpret_cast<GroupLds*>(smem));
     __syncthreads();
-    FSTAMP(2);
+    st.grouped();
   }
   const pvt_round R = *reinterpret_cast<const pvt_round*>(F.dev + fr.desc);   // (n_groups set)
   fused_place<MODE, HPL, WIDE>(F, R);
   __syncthreads();
-  FSTAMP(3);
+  st.placed();
   block_copy2<16>(const_cast<char*>(F.hmap), F.dev, fr.out_lo, fr.out_hi - fr.out_lo, 0, 0);
   __syncthreads();
-  FSTAMP(4);
-#undef FSTAMP
+  st.results_out(F.ra.stamps);
 }
 
 #ifndef PVT_RESIDENT_WIDE_TU

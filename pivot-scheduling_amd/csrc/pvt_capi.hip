@@ -21,6 +21,7 @@
 #include "pvt_meter.h"
 #include "pvt_usage.h"
 #include "pvt_hostops.h"
+#include "pvt_stamps.h"
 
 int pvt::fail(pvt_ctx* c, int code, const char* fmt, ...) {
   char buf[512];
@@ -321,9 +322,7 @@ extern "C" int pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills) 
 extern "C" int pvt_debug_commit_stamps(pvt_ctx* ctx, uint64_t* out, int n) {
   if (!ctx || !out || n < 8) return PVT_EINVAL;
 #ifdef PVT_STAMPS
-  // 32 counters, then per-round cycles of the resident kernel (4096 rounds), then the frontier
-  // walk's per-chain words
-  constexpr int NW = ZW_STAMP_CHAIN + 8 * ZW_STAMP_CHAINS;
+  constexpr int NW = STAMP_WORDS;            // (the slot map: pvt_stamps.h)
   if (!ctx->stamps) {
     if (hipMalloc((void**)&ctx->stamps, sizeof(uint64_t) * NW) != hipSuccess) return PVT_ENOMEM;
     (void)hipMemset(ctx->stamps, 0, sizeof(uint64_t) * NW);

@@ -370,11 +370,6 @@ struct ZwalkArgs {
   const int32_t* zcomp;
 };
 constexpr int ZW_CERT_FAST = 1 << 8;
-// PVT_STAMPS builds: chain b's own words in the stamps buffer, 8 from ZW_STAMP_CHAIN + 8 b (past
-// the 32 counters and the resident kernel's 4096 rounds): run_bulk calls, continued-run calls,
-// cycles between calls, cycles of the continued calls with the gap before each, walk cycles,
-// tasks walked, chain tasks
-constexpr int ZW_STAMP_CHAIN = 32 + 4096, ZW_STAMP_CHAINS = 64;
 constexpr int ZW_MIN_PARTS = 256;
 // per-dimension minima of avail over hosts [lo, hi) into part[ZW_MIN_PARTS][4]
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);

@@ -18,6 +18,7 @@
 #include "pvt_kernels.h"
 #include "pvt_zwin_dev.h"
 #include "pvt_list.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
@@ -1424,19 +1425,6 @@ __device__ void zone_window_block(const PrepArgs& A, const GatherOut& O, int j, 
   if (tid == 0) { w.n = n; w.bad = bad ? 1 : 0; }
 }
 
-#ifdef PVT_STAMPS
-__device__ __forceinline__ uint64_t gstamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define GSTAMP(k) do { if (g == 0 && tid == 0 && O.stamps) { const uint64_t t_ = gstamp(); gph[k] = t_ - gtl; gtl = t_; } } while (0)
-#else
-#define GSTAMP(k) do {} while (0)
-#endif
-
 // The grouped order of a round with few groups (G <= GCOMPACT_MAX, after order_count_kernel):
 // block g scans every task's group (T reads from L2, G of them in all), collects its own
 // (sort key, task) pairs in LDS by wave-aggregated cursors, fills their placement with -1,
@@ -1458,10 +1446,8 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
   }
   const int g = blockIdx.x - 1, tid = threadIdx.x, lane = tid & 63;
   const int T = A.T;
-#ifdef PVT_STAMPS
-  uint64_t gph[4] = {0, 0, 0, 0}, gtl = 0;
-  if (g == 0 && tid == 0) gtl = gstamp();
-#endif
+  OrderStamps st;                             // (make stamps: group 0's phases, pvt_stamps.h)
+  st.begins(O.stamps, g, tid);
   const int nmin = O.hmin ? ZW_MIN_PARTS : 0;
   if (g >= A.G + nmin) {                      // the first epoch's zero-cost windows
     zone_window_block(A, O, g - A.G - nmin, reinterpret_cast<int32_t*>(k));
@@ -1509,7 +1495,7 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
     }
   if (tid == 0) { fill = 0; below_s = 0; }
   __syncthreads();
-  GSTAMP(0);
+  st.set_up();
   const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
   constexpr int PB = 8;
   for (int i0 = 0; i0 < T; i0 += 1024 * PB) {
@@ -1562,9 +1548,9 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
     k[q] = key;
   }
   __syncthreads();
-  GSTAMP(1);
+  st.keys_built();
   lds_sort_pairs(k, v, n);
-  GSTAMP(2);
+  st.sorted();
   const int a = below_s;
   const int32_t anc = A.ganc[g];
   // The group's certificate (GroupCert) from the rows this loop holds anyway: a wave's 64 lanes of
@@ -1652,12 +1638,7 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
       }
     }
   }
-#ifdef PVT_STAMPS
-  __syncthreads();
-  GSTAMP(3);
-  if (g == 0 && tid == 0 && O.stamps)
-    for (int q = 0; q < 4; q++) atomicAdd((unsigned long long*)&O.stamps[16 + q], (unsigned long long)gph[q]);
-#endif
+  st.gathered(O.stamps);
 }
 void launch_group_sort_gather(const PrepArgs& a, const GatherOut& o, hipStream_t st) {
   const int extra = (o.hmin ? ZW_MIN_PARTS : 0) + (o.zwin ? a.Z : 0);

@@ -31,6 +31,7 @@
 
 #include "pvt_device.h"
 #include "pvt_kernels.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
@@ -87,24 +88,9 @@ __device__ __forceinline__ void lw_key(double a0, double a1, double a2, double a
   k2 = ((uint64_t)tb << 32) | (uint32_t)id;
 }
 
-#ifdef PVT_STAMPS
-__device__ __forceinline__ uint64_t lstamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#endif
-
 __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
-#ifdef PVT_STAMPS
-  uint64_t ph[4] = {0, 0, 0, 0}, n_task = 0, n_load = 0, n_liveit = 0, n_twin = 0, n_live = 0;
-  uint64_t ts = lstamp();
-#define LW_PHASE(k) do { const uint64_t t2 = lstamp(); ph[k] += t2 - ts; ts = t2; } while (0)
-#else
-#define LW_PHASE(k) ((void)0)
-#endif
+  LwalkStamps st;                              // (make stamps: phases and counts, pvt_stamps.h)
+  st.begins();
   extern __shared__ __attribute__((aligned(16))) char smem[];
   LwalkLDS& S = *reinterpret_cast<LwalkLDS*>(smem);
   const int lane = lane_id();
@@ -162,9 +148,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
     ce0 = e->a[0]; ce1 = e->a[1]; ce2 = e->a[2]; ce3 = e->a[3];
     ce_u = v && lw_find(S, ce_id) < 0;
     cw = w; cbase = base; ccnt = cnt;
-#ifdef PVT_STAMPS
-    n_load++;
-#endif
+    st.chunk_loaded();
   };
 
   // task records, 64 per batch in lanes (lane l: task b0 + l's demand, list count, completeness,
@@ -229,11 +213,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
       ccomp = comp;
       pd0 = d0; pd1 = d1; pd2 = d2; pd3 = d3;
     }
-#ifdef PVT_STAMPS
-    n_task++;
-    n_live += nlive;
-#endif
-    LW_PHASE(0);
+    st.task_read(nlive);
     // the first untouched entry at or after the cursor
     int L = -1;
     for (;;) {
@@ -283,10 +263,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
       n_own += Rb;
       k += Rb - 1;                               // (the loop adds the last one)
       lw_fence();
-#ifdef PVT_STAMPS
-      n_task += Rb - 1;
-#endif
-      LW_PHASE(3);
+      st.run_placed(Rb);
       continue;
     }
     uint64_t b1 = ~0ull, b2 = ~0ull;
@@ -294,13 +271,11 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
       b1 = readlane_u64((uint64_t)__double_as_longlong(ce_s), L);
       b2 = ((uint64_t)readlane_u(ce_tb, L) << 32) | (uint32_t)readlane_i(ce_id, L);
     }
-    LW_PHASE(1);
+    st.picked();
     // live touched hosts, rescored exactly
     int wq = -1;
     for (int q0 = 0; q0 < nlive; q0 += WAVE) {
-#ifdef PVT_STAMPS
-      n_liveit++;
-#endif
+      st.live_iteration();
       const int qi = q0 + lane;
       const int q = qi < nlive ? S.live[qi] : 0;
       const double a0 = S.ta[0][q], a1 = S.ta[1][q], a2 = S.ta[2][q], a3 = S.ta[3][q];
@@ -316,10 +291,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
         b1 = mk1; b2 = mk2;
       }
     }
-    LW_PHASE(2);
-#ifdef PVT_STAMPS
-    n_twin += wq >= 0;
-#endif
+    st.rescored(wq >= 0);
     if (L < 0 && wq < 0) {                     // no host fits: the task waits
       if (lane == 0) A.placement[caller] = -1;
       continue;
@@ -376,7 +348,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
     }
     if (lane == 0) A.placement[caller] = wid;
     lw_fence();                                // this commit's LDS writes before the next reads
-    LW_PHASE(3);
+    st.committed();
   }
   }
   // the capacities of the hosts this walk committed to
@@ -396,17 +368,7 @@ __global__ __launch_bounds__(WAVE) void lwalk_kernel(CommitArgs A) {
       __hip_atomic_store(A.hflag, A.hseq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
-#ifdef PVT_STAMPS
-  if (lane == 0 && A.stamps) {
-    for (int k = 0; k < 4; k++) atomicAdd((unsigned long long*)&A.stamps[k], (unsigned long long)ph[k]);
-    atomicAdd((unsigned long long*)&A.stamps[4], (unsigned long long)n_task);
-    atomicAdd((unsigned long long*)&A.stamps[5], (unsigned long long)n_load);
-    atomicAdd((unsigned long long*)&A.stamps[6], (unsigned long long)n_liveit);
-    atomicAdd((unsigned long long*)&A.stamps[7], (unsigned long long)n_twin);
-    atomicAdd((unsigned long long*)&A.stamps[8], (unsigned long long)n_live);
-  }
-#endif
-#undef LW_PHASE
+  st.walk_ends(A.stamps, lane);
 }
 
 constexpr size_t LWALK_LDS_BYTES = sizeof(LwalkLDS);

@@ -17,6 +17,7 @@
 #include "pvt_kernels.h"
 #include "pvt_mt.h"
 #include "pvt_opp.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
@@ -270,24 +271,6 @@ __device__ __forceinline__ int count_lost(const OppLDS& S, int m, double d0, dou
   return n;
 }
 
-#ifdef PVT_STAMPS
-__device__ __forceinline__ uint64_t ostamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define OSTAMP(k)                         \
-  do {                                    \
-    const uint64_t t_ = ostamp();         \
-    ph[k] += t_ - tl;                     \
-    tl = t_;                              \
-  } while (0)
-#else
-#define OSTAMP(k) do {} while (0)
-#endif
-
 // One wave orders its own LDS operations: a compiler fence plus lgkmcnt(0). (__syncthreads
 // would also wait vmcnt(0).)
 __device__ __forceinline__ void wave_lds_fence() {
@@ -329,10 +312,8 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
   __syncthreads();
   const bool fast = A.nsq <= WAVE;   // one super-chunk count per lane (H <= 1,048,576)
   const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-#ifdef PVT_STAMPS
-  uint64_t ph[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  uint64_t tl = ostamp();
-#endif
+  OppStamps st;                       // (make stamps: the passes' cycles and counts, pvt_stamps.h)
+  st.begins();
 
   int s = 0;
   while (s < A.nt) {
@@ -395,7 +376,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       }
     }
     __syncthreads();
-    OSTAMP(0);
+    st.counted();
     // ---- pass 2 (wave 0): the draws, in task order, from the live state (saved first). Most
     // draws accept their first output (n is close to the mask's power of two), so each pending
     // draw is first tried against one buffered output (lane q: the (q - used)-th pending draw);
@@ -437,7 +418,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       mt_unbuffer(S.mt, mw);
     }
     __syncthreads();
-    OSTAMP(1);
+    st.drawn();
     // ---- pass 3 (all waves): super-chunk of k_j, its bitmaps, the OPP_C candidates from k_j on
     int qsel[OPP_TB], ksel[OPP_TB];
     uint64_t bits[OPP_TB][U];
@@ -526,7 +507,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
         for (int u = 0; u < U; u++) bits[t][u] = bp[u];
       }
     }
-    OSTAMP(5);
+    st.selected();
 #pragma unroll
     for (int t = 0; t < OPP_TB; t++) {
       const int j = s + wave * OPP_TB + t;
@@ -620,7 +601,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       if (lane == 0) S.ccount[j - s] = cc;
     }
     wave_lds_fence();
-    OSTAMP(6);
+    st.candidates_built();
     // candidates' capacity at the range start: lane = (candidate lane / 4, resource lane % 4);
     // touched hosts from the table, the others from HBM (the walk has not written them)
     double cv[OPP_TB];
@@ -640,7 +621,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       }
     }
     __syncthreads();
-    OSTAMP(2);
+    st.capacities_loaded();
     // ---- pass 4 (wave 0): walk the range. Lane l holds range task s + l: its demand, draw,
     // candidates (S.cav keeps their capacities current through the range's commits), the
     // candidates that stopped fitting (lm), the lost hosts below c_0 (mm) and its new-lost count
@@ -696,7 +677,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       uint64_t okm = __ballot(choose());
       uint64_t cmt = 0;
       int stop = e;
-      OSTAMP(9);
+      st.walk_set_up();
       int L = posm ? __builtin_ctzll(posm) : R;
       while (L < R) {   // (tasks without a feasible host at s place nothing and change nothing)
         if (!((okm >> L) & 1ull)) {   // the draw changed, or the answer lies beyond the
@@ -722,11 +703,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
         const uint64_t fn = __ballot(m0 >= e0) & __ballot(m1 >= e1) & __ballot(m2 >= e2) & __ballot(m3 >= e3);
         const uint64_t lostm = am & fw & ~fn;
         const uint64_t rngm = am & __ballot(cw >= c0l) & __ballot(cw <= cmax);
-#ifdef PVT_STAMPS
-        ph[13] += 1;
-        ph[11] += lostm ? 1 : 0;
-        ph[12] += rngm ? 1 : 0;
-#endif
+        st.commit_checked(lostm, rngm);
         if (lostm | rngm) {
           const bool lost = (lostm >> lane) & 1ull;
           if ((rngm >> lane) & 1ull) {   // cw's capacity is now m; a lost cw stops fitting
@@ -755,7 +732,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
         }
         L = Ln;
       }
-      OSTAMP(8);
+      st.walked();
       // the range's commits: lane l's row still holds its choice (later commits only rewrite
       // the rows of the tasks after them)
       int rch = -1;
@@ -817,10 +794,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
       }
     }
     __syncthreads();
-    OSTAMP(3);
-#ifdef PVT_STAMPS
-    ph[4] += 1;
-#endif
+    st.range_done();
     s = S.ctl[0];
   }
   // the window's commits (hosts this walk touched): to global availability, or handed to the
@@ -848,13 +822,7 @@ __global__ __launch_bounds__(OPP_NW * WAVE) void opp_commit_kernel(OppCommitArgs
   }
   for (int i = tx; i < A.nt; i += NT) A.placement[i] = S.pl[i];
   for (int i = tx; i < 625; i += NT) A.mt[i] = S.mt[i];
-#ifdef PVT_STAMPS
-  if (tx == 0 && A.stamps) {
-    for (int k = 0; k < 14; k++)
-      if (k != 7) atomicAdd((unsigned long long*)&A.stamps[k], (unsigned long long)ph[k]);
-    atomicAdd((unsigned long long*)&A.stamps[7], (unsigned long long)A.nt);
-  }
-#endif
+  st.walk_ends(A.stamps, tx, A.nt);
 }
 
 hipError_t opp_init_attrs() {

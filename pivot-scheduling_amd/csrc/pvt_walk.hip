@@ -41,6 +41,7 @@
 
 #include "pvt_device.h"
 #include "pvt_kernels.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
@@ -164,25 +165,6 @@ __device__ __forceinline__ double rec_d(int32_t tv, int k) {
   const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane(tv, 2 * k + 1);
   return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
-
-#ifdef PVT_STAMPS
-// Diagnostic build only (make stamps): per-phase cycle sums of the walker.
-__device__ __forceinline__ uint64_t stamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-#define STAMP(k)                          \
-  do {                                    \
-    const uint64_t t_ = stamp();          \
-    ph[k] += t_ - tl;                     \
-    tl = t_;                              \
-  } while (0)
-#else
-#define STAMP(k) do {} while (0)
-#endif
 
 // Window index of the walk's i-th task (epoch chains walk a subsequence of the window).
 __device__ __forceinline__ int widx(const CommitArgs& A, int i) { return A.cmap ? A.cmap[i] : i; }
@@ -646,11 +628,8 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
     X[r].alive = false; X[r].a0 = X[r].a1 = X[r].a2 = X[r].a3 = 0.0; X[r].c = 0.0; X[r].b = 1.0;
   }
 
-#ifdef PVT_STAMPS
-  uint64_t ph[5] = {0, 0, 0, 0, 0};
-  uint64_t nl_sum = 0;
-  uint64_t tl = stamp();
-#endif
+  CommitStamps st;                            // (make stamps: the walker's phases, pvt_stamps.h)
+  st.begins();
   for (int i = 0; i < A.nt; i++) {
     const int slot = i % RING;
     for (int spin = 0; __builtin_amdgcn_readfirstlane(vload(&S.flag[slot])) != i ||
@@ -670,7 +649,7 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
     const int caller = __builtin_amdgcn_readlane(tv, 11);
     const int grp = __builtin_amdgcn_readlane(tv, 18);   // realtime_bw: the task's group
     const int nU = rdw(rs, R_NU);
-    STAMP(0);
+    st.slot_read();
 
     auto patched = [&](int32_t id) {
       bool p = false;
@@ -722,7 +701,7 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
                             (uint32_t)rdw(rs, tb_ + RF_ID);
         if (key_lt(c1, c2, t1, t2)) { t1 = c1; t2 = c2; wrec = tb_; }
       }
-      STAMP(1);
+      st.looked_up();
       // the patched hosts, rescored exactly (independent chains: the compiler interleaves them)
       uint64_t k1[NP], k2[NP];
 #pragma unroll
@@ -753,7 +732,7 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
 #pragma unroll
       for (int r = 0; r < NP; r++)
         if (xf[r] && key_lt(k1[r], k2[r], t1, t2)) { t1 = k1[r]; t2 = k2[r]; wx = r; wrec = -1; }
-      STAMP(2);
+      st.picked();
       if (wrec < 0 && wx < 0) {
         if (exhausted) refill = true;         // refill from here
         else none = true;                     // no host fits: the task waits
@@ -776,8 +755,8 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
             if (o == pr && xf[o]) wx = o;
         }
       }
-      STAMP(1);
-      STAMP(2);
+      st.looked_up();
+      st.picked();
       if (wrec < 0 && wx < 0) {
         if (!comp) refill = true;
         else none = true;
@@ -799,8 +778,7 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
       X[0].id = -1; X[0].alive = false; X[0].anc = -1;
       cbarrier();
       if (lane == 0) vstore(&S.committed, i + 1);
-      STAMP(3);
-      STAMP(4);
+      st.waits();
       continue;
     }
 
@@ -829,7 +807,7 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
         W.hp = __builtin_amdgcn_readfirstlane(p);
       }
     }
-    STAMP(3);
+    st.rescored();
 
     // commit: resc[h] -= t_demand (cost_aware.py:95,126; vbp.py:24,49)
     const double n0 = W.a0 - d0, n1 = W.a1 - d1, n2 = W.a2 - d2, n3 = W.a3 - d3;
@@ -885,23 +863,14 @@ __device__ void walk(const CommitArgs& A, WalkLDS& S) {
     X[0].a0 = n0; X[0].a1 = n1; X[0].a2 = n2; X[0].a3 = n3;
     cbarrier();
     if (lane == 0) vstore(&S.committed, i + 1);   // after every LDS write of this commit
-#ifdef PVT_STAMPS
-    nl_sum += nl;
-#endif
-    STAMP(4);
+    st.committed(nl);
   }
   if (lane == 0) {
     vstore(&S.stop, 1);
     A.status[0] = status;
     A.status[1] = n_own;
   }
-#ifdef PVT_STAMPS
-  if (lane == 0 && A.stamps) {
-    for (int k = 0; k < 5; k++) atomicAdd((unsigned long long*)&A.stamps[k], (unsigned long long)ph[k]);
-    atomicAdd((unsigned long long*)&A.stamps[5], (unsigned long long)(status < 0 ? 0 : status));
-    atomicAdd((unsigned long long*)&A.stamps[6], (unsigned long long)nl_sum);
-  }
-#endif
+  st.walk_ends(A.stamps, lane, status);
 }
 
 template <int MODEP>

@@ -7,18 +7,11 @@
 
 #include "pvt_device.h"
 #include "pvt_kernels.h"
+#include "pvt_stamps.h"
 
 namespace pvt {
 
 #ifdef PVT_STAMPS
-__device__ __forceinline__ uint64_t zstamp() {
-  uint64_t t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-
 struct ZwStamps {
   uint64_t t_start = 0, t_load = 0, t_cert = 0, t_win = 0, t_cap = 0, t_walk = 0;
   uint64_t n_chunks = 0, n_switch = 0, n_bulk = 0, n_runs = 0;
@@ -36,44 +29,44 @@ struct ZwStamps {
   int panc = -1, prr = 0;
 
   // phases of the prologue (the fast prologue's window is part of its entry loads)
-  __device__ __forceinline__ void start() { t_start = zstamp(); }
-  __device__ __forceinline__ void loaded() { t_load = zstamp(); }
-  __device__ __forceinline__ void certified() { t_cert = zstamp(); }
-  __device__ __forceinline__ void certified_fast() { t_cert = t_win = t_cap = zstamp(); }
-  __device__ __forceinline__ void window_built() { t_win = zstamp(); }
-  __device__ __forceinline__ void capacities_loaded() { t_cap = zstamp(); }
-  __device__ __forceinline__ void walk_begins() { t_walk = zstamp(); }
+  __device__ __forceinline__ void start() { t_start = cycle_stamp(); }
+  __device__ __forceinline__ void loaded() { t_load = cycle_stamp(); }
+  __device__ __forceinline__ void certified() { t_cert = cycle_stamp(); }
+  __device__ __forceinline__ void certified_fast() { t_cert = t_win = t_cap = cycle_stamp(); }
+  __device__ __forceinline__ void window_built() { t_win = cycle_stamp(); }
+  __device__ __forceinline__ void capacities_loaded() { t_cap = cycle_stamp(); }
+  __device__ __forceinline__ void walk_begins() { t_walk = cycle_stamp(); }
 
   // run_bulk: entry (k: the call's first ring position), the ends of its parts, exit
   __device__ __forceinline__ void bulk_enter(int k) {
-    tA = zstamp();
+    tA = cycle_stamp();
     gap = t_ret ? tA - t_ret : 0;
     contd = (Ec >> (k & 63)) & 1ull;
     n_calls++;
     st_between += gap;
   }
-  __device__ __forceinline__ void bulk_setup_done() { tA1 = zstamp(); st_setup += tA1 - tA; }
-  __device__ __forceinline__ void bulk_pass1_done(int t) { n_iter += t; st_loop += zstamp() - tA1; }
-  __device__ __forceinline__ void bulk_counted() { tB = zstamp(); st_p1 += tB - tA; }
+  __device__ __forceinline__ void bulk_setup_done() { tA1 = cycle_stamp(); st_setup += tA1 - tA; }
+  __device__ __forceinline__ void bulk_pass1_done(int t) { n_iter += t; st_loop += cycle_stamp() - tA1; }
+  __device__ __forceinline__ void bulk_counted() { tB = cycle_stamp(); st_p1 += tB - tA; }
   __device__ __forceinline__ void bulk_assigned(int asg, int cnt, uint64_t over) {
     const uint64_t part = __ballot(asg > 0 && asg < cnt);
     n_part += part != 0;
     if (part) s_pasg += (uint64_t)__builtin_amdgcn_readlane(asg, __builtin_ctzll(part));
     n_fromc += over != 0;
-    tC = zstamp();
+    tC = cycle_stamp();
     st_who += tC - tB;
   }
   __device__ __forceinline__ void bulk_replay_block() { n_rep += 4; }
-  __device__ __forceinline__ void bulk_replayed() { st_rep += zstamp() - tC; }
+  __device__ __forceinline__ void bulk_replayed() { st_rep += cycle_stamp() - tC; }
   __device__ __forceinline__ void bulk_exit() {
-    t_ret = zstamp();
+    t_ret = cycle_stamp();
     st_p2 += t_ret - tB;
     if (contd) { n_cont++; st_cont += gap + (t_ret - tA); }
   }
 
   // a batch's head and tail (records, run masks, log flush)
-  __device__ __forceinline__ void batch_part_begins() { tb0 = zstamp(); }
-  __device__ __forceinline__ void batch_part_ends() { st_batch += zstamp() - tb0; }
+  __device__ __forceinline__ void batch_part_begins() { tb0 = cycle_stamp(); }
+  __device__ __forceinline__ void batch_part_ends() { st_batch += cycle_stamp() - tb0; }
   // Ec: E, and the batch's first task against the last batch's last
   __device__ __forceinline__ void batch_runs(uint64_t E, int i0, int kn, int lane, double d0, double d1,
                                              double d2, double d3, int tanc, int trr, bool rrm,
@@ -95,8 +88,8 @@ struct ZwStamps {
   }
 
   // the walk's paths (run_placed: a run of that many tasks, 0: none)
-  __device__ __forceinline__ void search_begins() { t0 = zstamp(); }
-  __device__ __forceinline__ void search_ends() { st_search += zstamp() - t0; }
+  __device__ __forceinline__ void search_begins() { t0 = cycle_stamp(); }
+  __device__ __forceinline__ void search_ends() { st_search += cycle_stamp() - t0; }
   __device__ __forceinline__ void probe() { n_probe++; }
   __device__ __forceinline__ void run_placed(int tasks) { n_chunks += tasks; n_bulk += tasks; n_runs += tasks > 0; }
   __device__ __forceinline__ void single_placed() { n_chunks++; n_single++; }
@@ -106,7 +99,7 @@ struct ZwStamps {
   // the sums, by one lane of the chain's walker (slot 28 is unused)
   __device__ __forceinline__ void add_to(uint64_t* stamps, int b, int done, int nt) {
     if (!stamps) return;
-    const uint64_t t_end = zstamp();
+    const uint64_t t_end = cycle_stamp();
     auto add = [&](int slot, uint64_t v) {
       atomicAdd((unsigned long long*)&stamps[slot], (unsigned long long)v);
     };

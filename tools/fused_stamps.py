@@ -14,6 +14,7 @@ from pivot_place.engine import PlacementEngine  # noqa: E402
 name = sys.argv[1] if len(sys.argv) > 1 else "sim_c1_cost_aware"
 eng = PlacementEngine(0, lib_path=os.environ.get("STAMPS_LIB") or os.path.join(
     ROOT, "pivot-scheduling_amd", "diag", "libpivot_place_stamps.so"))
+# (slot numbers below: the slot map in pivot-scheduling_amd/csrc/pvt_stamps.h)
 f = eng.lib.pvt_debug_commit_stamps
 f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
 buf = (ctypes.c_uint64 * 32)()

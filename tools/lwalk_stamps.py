@@ -16,6 +16,7 @@ H = int(sys.argv[1]) if len(sys.argv) > 1 else 1_000_000
 T = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000
 eng = PlacementEngine(0, lib_path=os.path.join(ROOT, "pivot-scheduling_amd", "diag",
                                                "libpivot_place_stamps.so"))
+# (slot numbers below: the slot map in pivot-scheduling_amd/csrc/pvt_stamps.h)
 f = eng.lib.pvt_debug_commit_stamps
 f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
 buf = (ctypes.c_uint64 * 16)()

@@ -21,6 +21,7 @@ H = int(sys.argv[3]) if len(sys.argv) > 3 else 1000
 T = int(sys.argv[4]) if len(sys.argv) > 4 else 1000
 eng = PlacementEngine(0, lib_path=os.environ.get("STAMPS_LIB") or os.path.join(
     ROOT, "pivot-scheduling_amd", "diag", "libpivot_place_stamps.so"))
+# (slot numbers below: the slot map in pivot-scheduling_amd/csrc/pvt_stamps.h)
 f = eng.lib.pvt_debug_commit_stamps
 f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
 NW = 32 + 4096

@@ -17,9 +17,10 @@ lib = sys.argv[3] if len(sys.argv) > 3 else "libpivot_place_stamps.so"
 MODES = {"ca_ff": _abi.PVT_CA_FF, "ca_bf": _abi.PVT_CA_BF, "vbp_ff": _abi.PVT_VBP_FF}
 mode = sys.argv[4] if len(sys.argv) > 4 else "ca_bf"
 eng = PlacementEngine(0, lib_path=os.path.join(ROOT, "pivot-scheduling_amd", "diag", lib))
+# (slot numbers below: the slot map in pivot-scheduling_amd/csrc/pvt_stamps.h)
 f = eng.lib.pvt_debug_commit_stamps
 f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64), ctypes.c_int]
-CHAIN0, CHAINS = 32 + 4096, 64     # ZW_STAMP_CHAIN, ZW_STAMP_CHAINS (csrc/pvt_kernels.h)
+CHAIN0, CHAINS = 32 + 4096, 64     # ZW_STAMP_CHAIN, ZW_STAMP_CHAINS (csrc/pvt_stamps.h)
 NW = CHAIN0 + 8 * CHAINS
 buf = (ctypes.c_uint64 * NW)()
 assert f(eng.ctx, buf, NW) == 0
