@@ -363,8 +363,9 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
         q0 = fmin(q0, __shfl_xor(q0, off)); q1 = fmin(q1, __shfl_xor(q1, off));
         q2 = fmin(q2, __shfl_xor(q2, off)); q3 = fmin(q3, __shfl_xor(q3, off));
       }
-      const bool sep = (q0 - wx[b * 4 + 0] >= 0x1p-288) || (q1 - wx[b * 4 + 1] >= 0x1p-288) ||
-                       (q2 - wx[b * 4 + 2] >= 0x1p-288) || (q3 - wx[b * 4 + 3] >= 0x1p-288);
+      // (cert_separates, written out: pvt_cert.h)
+      const bool sep = (q0 - wx[b * 4 + 0] >= CERT_SEP) || (q1 - wx[b * 4 + 1] >= CERT_SEP) ||
+                       (q2 - wx[b * 4 + 2] >= CERT_SEP) || (q3 - wx[b * 4 + 3] >= CERT_SEP);
       if (__builtin_amdgcn_readfirstlane((int)!sep)) return;
       store_chunk(p0);
       const uint64_t below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
@@ -432,7 +433,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
             if (lane < Z) {
               const double c = csum[a * Z + lane], bw = bsum[a * Z + lane];
               zc = c == 0.0;
-              sf = bw > 0.0 && bw <= 0x1p+300 && (c == 0.0 || (c >= 0x1p-300 && c < DINF));
+              sf = cert_safe_slot(c, bw);
             }
             zc_z = (uint32_t)__ballot(zc);
             sf_z = (uint32_t)__ballot(sf);
@@ -454,8 +455,8 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
         if (bulk && dense && k + 1 < kn && ((E >> (k + 1)) & 1ull) && d0 >= 0.0 && d1 >= 0.0 &&
             d2 >= 0.0 && d3 >= 0.0) {
           const uint64_t m0 = __ballot(rv && ra0 >= d0 && ra1 >= d1 && ra2 >= d2 && ra3 >= d3);
-          const uint64_t big = __ballot(rv && !(ra0 <= 0x1p+500 && ra1 <= 0x1p+500 &&
-                                                ra2 <= 0x1p+500 && ra3 <= 0x1p+500));
+          const uint64_t big = __ballot(rv && !(ra0 <= CERT_BOUND && ra1 <= CERT_BOUND &&
+                                                ra2 <= CERT_BOUND && ra3 <= CERT_BOUND));
           if (m0 != 0 && (m0 & big) == 0) {
             const int R = min(kn - k, 1 + (int)__builtin_ctzll(~(E >> (k + 1))));
             int pre, asg;
@@ -497,7 +498,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
           if (F) {
             const int w = __builtin_ctzll(F);
             const double x0 = ra0 - d0, x1 = ra1 - d1, x2 = ra2 - d2, x3 = ra3 - d3;
-            if (__ballot(lane == w && (x0 > 0x1p+500 || x1 > 0x1p+500 || x2 > 0x1p+500 || x3 > 0x1p+500))) {
+            if (__ballot(lane == w && (x0 > CERT_BOUND || x1 > CERT_BOUND || x2 > CERT_BOUND || x3 > CERT_BOUND))) {
               win = -2;                         // (a huge residual: the score need not be 0)
             } else {
               if (lane == w) { ra0 = x0; ra1 = x1; ra2 = x2; ra3 = x3; }   // resc[h] -= d
@@ -514,7 +515,7 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
               if (F2) {
                 const int w = __builtin_ctzll(F2);
                 const double x0 = y0 - d0, x1 = y1 - d1, x2 = y2 - d2, x3 = y3 - d3;
-                if (__ballot(lane == w && (x0 > 0x1p+500 || x1 > 0x1p+500 || x2 > 0x1p+500 || x3 > 0x1p+500))) {
+                if (__ballot(lane == w && (x0 > CERT_BOUND || x1 > CERT_BOUND || x2 > CERT_BOUND || x3 > CERT_BOUND))) {
                   win = -2;
                 } else {
                   if (lane == w) { wa[h] = x0; wa[RW_MAXH + h] = x1; wa[2 * RW_MAXH + h] = x2; wa[3 * RW_MAXH + h] = x3; }
@@ -536,10 +537,10 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
             const int w = __builtin_ctzll(C);
             const uint64_t Lx = F & ~m_zs & ((1ull << w) - 1ull);
             const double x0 = ra0 - d0, x1 = ra1 - d1, x2 = ra2 - d2, x3 = ra3 - d3;
-            const uint64_t tight = __ballot(x0 < 0x1p-300) & __ballot(x1 < 0x1p-300) &
-                                   __ballot(x2 < 0x1p-300) & __ballot(x3 < 0x1p-300);
-            const uint64_t huge = __ballot(x0 > 0x1p+500) | __ballot(x1 > 0x1p+500) |
-                                  __ballot(x2 > 0x1p+500) | __ballot(x3 > 0x1p+500);
+            const uint64_t tight = __ballot(x0 < CERT_RES_MIN) & __ballot(x1 < CERT_RES_MIN) &
+                                   __ballot(x2 < CERT_RES_MIN) & __ballot(x3 < CERT_RES_MIN);
+            const uint64_t huge = __ballot(x0 > CERT_BOUND) | __ballot(x1 > CERT_BOUND) |
+                                  __ballot(x2 > CERT_BOUND) | __ballot(x3 > CERT_BOUND);
             if (!(Lx & (~m_sf | tight)) && !((huge >> w) & 1ull)) {
               if (lane == w) { ra0 = x0; ra1 = x1; ra2 = x2; ra3 = x3; }   // resc[h] -= d
               win = p0 * 64 + w;
@@ -553,8 +554,8 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
           const bool f = v && fits<false>(x0, x1, x2, x3, d0, d1, d2, d3);   // (>=, cost_aware.py:91)
           const double mx = fmax(fmax(x0 - d0, x1 - d1), fmax(x2 - d2, x3 - d3));
           const bool sf = (sf_z >> z) & 1u, zc = (zc_z >> z) & 1u;
-          const bool zz = sf && ((zc && mx <= 0x1p+500) || mx == 0.0);
-          const bool risky = f && !zz && (!sf || !(mx >= 0x1p-300) || zc);
+          const CertClass k = cert_classify(f, sf, zc, mx);
+          const bool zz = k.zero, risky = k.risky;
           zm = __ballot(f && zz);
           rk = __ballot(risky);
         };
@@ -1131,11 +1132,10 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
             zmask = 0; rmask = 0;
 #pragma unroll
             for (int j = 0; j < HPL; j++) {
-              // safe: bw in (0, 2^300] and c == 0 or c in [2^-300, inf): then a fitting host
-              // scores exactly +0 iff c == 0 or s2 == 0 (s2 finite), and otherwise >= 2^-900
-              // unless s2 < 2^-600
-              const bool safe = bb[j] > 0.0 && bb[j] <= 0x1p+300 &&
-                                (cc[j] == 0.0 || (cc[j] >= 0x1p-300 && cc[j] < DINF));
+              // safe (cert_safe_slot, written out: pvt_cert.h): then a fitting host scores exactly
+              // +0 iff c == 0 or s2 == 0 (s2 finite), and otherwise >= 2^-900 unless s2 < 2^-600
+              const bool safe = bb[j] > 0.0 && bb[j] <= CERT_BW_MAX &&
+                                (cc[j] == 0.0 || (cc[j] >= CERT_C_MIN && cc[j] < DINF));
               zmask |= ((safe && cc[j] == 0.0) ? 1u : 0u) << j;
               rmask |= (safe ? 0u : 1u) << j;
             }
@@ -1233,19 +1233,15 @@ __device__ __forceinline__ void resident_round(const ResidentArgs& A, const pvt_
         int c = 0x7fffffff;
         bool risky = false;
         if (MODE == CA_BF) {
-          // from the largest residual mx = max(a - d) of a fitting host (all residuals >= +0):
-          // mx == 0 is an exact fit (s2 == 0, score 0); mx >= 2^-300 gives s2 >= 2^-600 (the FMA
-          // chain only adds non-negative terms), so with a safe slot and c > 0 the score is
-          // >= 2^-900; with c == 0 the score is 0 while s2 is finite (mx <= 2^500). Anything
-          // else is risky and goes to the full path.
+          // zero class or risky, from the largest residual of a fitting host (pvt_cert.h)
 #pragma unroll
           for (int j = HPL - 1; j >= 0; j--) {     // (descending: the lowest candidate slot wins)
             const bool f = fits<false>(a0[j], a1[j], a2[j], a3[j], d0, d1, d2, d3);
             const double mx = fmax(fmax(a0[j] - d0, a1[j] - d1), fmax(a2[j] - d2, a3[j] - d3));
             const bool safe = !((rmask >> j) & 1u), zc = (zmask >> j) & 1u;
-            const bool z = safe && ((zc && mx <= 0x1p+500) || mx == 0.0);
-            c = (f && z) ? h0 + j : c;
-            risky |= f && !z && (!safe || !(mx >= 0x1p-300) || zc);
+            const CertClass k = cert_classify(f, safe, zc, mx);
+            c = (f && k.zero) ? h0 + j : c;
+            risky |= k.risky;
           }
           // (a non-finite demand can leave a NaN residual that fmax drops: full path)
           risky |= !(__builtin_fabs(d0) < DINF && __builtin_fabs(d1) < DINF &&

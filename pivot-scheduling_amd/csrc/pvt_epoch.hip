@@ -63,7 +63,7 @@ __device__ __forceinline__ bool beats(int32_t h, double f0, double f1, double f2
   const double s2 = norm2_seq(f0 - d0, f1 - d1, f2 - d2, f3 - d3);
   if (c == 0.0)   // zero egress cost: the score is exactly +0 (finite s2, bw > 0)
     return (0ull < w1) | ((0ull == w1) & (h < w.id));
-  if (w1 == 0ull && s2 >= 0x1p-600 && c >= 0x1p-300 && bw <= 0x1p300)
+  if (w1 == 0ull && cert_score_positive(c, s2, bw))
     return false;   // c * sqrt(s2) >= 2^-600 and / bw >= 2^-900: the score is > 0
   const double sc = (c * __builtin_sqrt(s2)) / bw;
   const uint64_t k1 = (uint64_t)__double_as_longlong(sc);
@@ -151,9 +151,8 @@ __global__ __launch_bounds__(256) void epoch_validate_kernel(EpochArgs A) {
           const double bw = rtrow ? rtrow[id] : A.bsum[a * A.Z + z];
           e_c[tid] = c;
           e_b[tid] = bw;
-          idonly = c >= 0x1p-300 && bw <= 0x1p300 &&
-                   (f0 - mx[0] >= 0x1p-287 || f1 - mx[1] >= 0x1p-287 ||
-                    f2 - mx[2] >= 0x1p-287 || f3 - mx[3] >= 0x1p-287);
+          idonly = c >= CERT_C_MIN && bw <= CERT_BW_MAX &&
+                   cert_separates(x.a, mx, CERT_MARGIN);
         }
       }
     }
@@ -252,8 +251,7 @@ __global__ __launch_bounds__(1024) void epoch_final_kernel(EpochArgs A) {
     const int sup = (h >= 0 && hv[fin_slot(h, hk)] != k) ? 1 : 0;
     A.wlog[s0 + k].sup = sup;
     if (A.cmax && h >= 0 && !sup &&
-        !(e.a[0] - gmx[0] >= 0x1p-287 || e.a[1] - gmx[1] >= 0x1p-287 ||
-          e.a[2] - gmx[2] >= 0x1p-287 || e.a[3] - gmx[3] >= 0x1p-287))
+        !cert_separates(e.a, gmx, CERT_MARGIN))
       unsafe = 1;                             // (benign race: every writer stores 1)
   }
   if (A.cmax) {

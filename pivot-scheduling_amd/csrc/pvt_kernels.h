@@ -11,6 +11,8 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 
+#include "pvt_cert.h"
+
 namespace pvt {
 
 // Timed launches (pvt_set_profiling 2: HIP events around one named kernel). Every launch helper
@@ -356,10 +358,10 @@ struct ZwalkArgs {
   // walked all its tasks writes its window's capacities to wb (the round's avail) itself; every
   // chain first saves its window's hosts and start capacities in undo[b], and reports status[0],
   // status[1] also to hstat[2b], hstat[2b + 1] and its certificate word to hcert[b] (both mapped
-  // pinned): bits 0-3 the dimensions no task of the chain demands (every d[r] is +-0), bits 4-7
-  // the dimensions whose host minimum is at least 2^-287 (best-fit; first-fit reports 0), bit 8
-  // (ZW_CERT_FAST) the chain took the fast prologue: it saved nothing in undo[b], its start rows
-  // are the prebuilt window's (cert.cwin[b]). hcert alone may be set (cert.fast without undo).
+  // pinned; bit fields: pvt_cert.h): the dimensions no task of the chain demands, the dimensions
+  // whose host minimum is at least CERT_MARGIN (best-fit; first-fit reports 0), and ZW_CERT_FAST:
+  // the chain took the fast prologue, it saved nothing in undo[b], its start rows are the
+  // prebuilt window's (cert.cwin[b]). hcert alone may be set (cert.fast without undo).
   struct ZwUndo* undo;
   int32_t* hstat;
   int32_t* hcert;
@@ -369,7 +371,6 @@ struct ZwalkArgs {
   // zero-cost component [Z] (the driver's zero_cost_components), else NULL
   const int32_t* zcomp;
 };
-constexpr int ZW_CERT_FAST = 1 << 8;
 constexpr int ZW_MIN_PARTS = 256;
 // per-dimension minima of avail over hosts [lo, hi) into part[ZW_MIN_PARTS][4]
 void launch_host_min(const double* avail, int H, int lo, int hi, double* part, hipStream_t st);

@@ -1417,7 +1417,7 @@ __device__ void zone_window_block(const PrepArgs& A, const GatherOut& O, int j, 
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const double x = O.avail[(size_t)r * O.H + h];
-      bad |= !(__builtin_fabs(x) <= 0x1p500);
+      bad |= !cert_bounded(x);
       w.a[r][p] = x;
     }
   }
@@ -1601,7 +1601,7 @@ __global__ __launch_bounds__(1024) void group_sort_gather_kernel(PrepArgs A, Gat
       for (int r = 0; r < 4; r++) {
         const double f = readlane_d(d[r], 0);
         const double x = i < n ? d[r] : f;
-        gbad |= !(__builtin_fabs(x) <= 0x1p500);
+        gbad |= !cert_bounded(x);
         gmx[r] = fmax(gmx[r], x);
         double m = f;
         if (__ballot(__double_as_longlong(x) != __double_as_longlong(f)) != 0) m = wave_min_d(x);

@@ -333,14 +333,14 @@ static bool tail_accepted(pvt_ctx* ctx, const EpochPlan& E, bool best_fit, uint6
   const int32_t* host = ctx->ep_host;
   const int nch = (int)E.segs.size();
   uint64_t w = 0;
-  int cert = 0xff;
+  int cert = ZW_CERT_EVERY_DIM;
   for (int c = 0; c < nch; c++) {
     if (host[EP_STATUS + 2 * c] == E.len[c] && host[EP_STATUS + 2 * c + 1] == 0) w |= 1ull << c;
     cert &= host[EP_CERT + c];
   }
   *wrote = w;
   const bool all = w == (nch >= 64 ? ~0ull : (1ull << nch) - 1ull);
-  return all && (!best_fit || ((cert & 0xf) & (cert >> 4)) != 0);
+  return all && (!best_fit || zw_cert_verdict(cert));
 }
 
 // A missed optimistic apply: the chains that wrote back get their start rows again, before the

@@ -186,11 +186,11 @@ __device__ __forceinline__ void put_rec(int32_t* res, int base, double s, uint32
 // their bit patterns order like the values (cost_aware.py:83, vbp.py:45).
 // The cost_aware score (c * sqrt(s2)) / bw without its square root and division where they
 // cannot matter: c == 0 (a zero-cost zone pair) gives exactly +0 (finite s2, bw > 0); and when
-// only a score of 0 can win (lim1 == 0, the bits of +0), c >= 2^-300, bw <= 2^300 and
-// s2 >= 2^-600 prove the score positive (>= 2^-900): the key is then "beats nothing" (~0).
+// only a score of 0 can win (lim1 == 0, the bits of +0), cert_score_positive (pvt_cert.h; written
+// out here) proves the score positive (>= 2^-900): the key is then "beats nothing" (~0).
 __device__ __forceinline__ uint64_t ca_score_bits(double c, double s2, double bw, uint64_t lim1) {
   if (c == 0.0) return 0ull;
-  if (lim1 == 0ull && c >= 0x1p-300 && bw <= 0x1p300 && s2 >= 0x1p-600) return ~0ull;
+  if (lim1 == 0ull && c >= CERT_C_MIN && bw <= CERT_BW_MAX && s2 >= CERT_S2_MIN) return ~0ull;
   return (uint64_t)__double_as_longlong((c * __builtin_sqrt(s2)) / bw);
 }
 

@@ -65,7 +65,6 @@ constexpr int ZW_WAVES = ZW_THREADS / 64;
 constexpr int ZW_SCAN = 8;                 // 16-byte zone loads (4 hosts) per thread per window-build pass
 constexpr int ZW_MINB = ZW_MIN_PARTS;      // blocks of the host-minimum pass
 constexpr int ZW_PR = 8;                   // chain task rows per thread per prologue pass
-constexpr double ZW_BIG = 0x1p500;
 
 #ifndef PVT_ZW_UNROLL
 #define PVT_ZW_UNROLL 8
@@ -563,9 +562,9 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
       }
       if (lane == 0) S.red[0][4 + wave] = v;   // (the chain's minimum: the certificate word)
     }
-    bool sep = false;
+    bool sep = false;                          // (cert_separates, written out: pvt_cert.h)
 #pragma unroll
-    for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= 0x1p-288);
+    for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= CERT_SEP);
     U = zu;
     // (it never walks a window it has not verified: the host's zone set inside the window's)
     const bool cover = zu != 0 && (A.cert.cu[b] & ~zu) == 0;
@@ -575,10 +574,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (tid == 0) {
       int cert = stop ? 0 : ZW_CERT_FAST;
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const double mnr = S.red[0][4 + r];
-        cert |= ((mx[r] <= 0.0 && mnr >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
-      }
+      for (int r = 0; r < 4; r++) cert |= zw_cert_dim(mx[r], S.red[0][4 + r], ha[r], r);
       if (A.hcert) A.hcert[b] = cert;
       if (stop) report(0, nt <= 0 ? 0 : 1);
     }
@@ -752,7 +748,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
             abits |= 1u << a;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-              bad |= !(__builtin_fabs(dv[u][r]) <= ZW_BIG);
+              bad |= !cert_bounded(dv[u][r]);
               mx[r] = fmax(mx[r], dv[u][r]);
               mn[r] = fmin(mn[r], dv[u][r]);
             }
@@ -802,7 +798,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         const int ga = W->gl[__builtin_ctz(m)];
         for (int z = tid; z < ZG; z += ZW_THREADS) {
           const double c = A.csum[ga * ZG + z], bw = A.bsum[ga * ZG + z];
-          if (W->zl[z] == ZL_NONE) out_bad |= !((c >= 0x1p-300) && (bw > 0.0) && (bw <= 0x1p300));
+          if (W->zl[z] == ZL_NONE) out_bad |= !((c >= CERT_C_MIN) && (bw > 0.0) && (bw <= CERT_BW_MAX));
         }
       }
       if (out_bad) S.bail = 1;
@@ -823,10 +819,11 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (!KEYED && A.cmax && tid < 4) A.cmax[b * 4 + tid] = mx[tid];   // (the validation's fast path)
     if (!KEYED && A.hcert && tid == 0) {       // the certificate word of the host's verdict
       int cert = 0;
-      if (!FF) {
+      if (!FF) {                               // (zw_cert_dim, written out: pvt_cert.h)
 #pragma unroll
         for (int r = 0; r < 4; r++)
-          cert |= ((mx[r] <= 0.0 && mn[r] >= 0.0) ? (1 << r) : 0) | ((ha[r] >= 0x1p-287) ? (16 << r) : 0);
+          cert |= ((mx[r] <= 0.0 && mn[r] >= 0.0) ? (ZW_CERT_UNDEMANDED << r) : 0) |
+                  ((ha[r] >= CERT_MARGIN) ? (ZW_CERT_HOSTMIN << r) : 0);
       }
       A.hcert[b] = cert;
     }
@@ -834,10 +831,10 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
     if (FF) {                                  // certificates (2') and (3'): bounded capacities,
       sep = true;                              // demands >= 0
 #pragma unroll
-      for (int r = 0; r < 4; r++) sep &= (ha[r] <= 0x1p298) && (mn[r] >= 0.0);
-    } else {
+      for (int r = 0; r < 4; r++) sep &= cert_ff_bounded(ha[r], mn[r]);
+    } else {                                   // (cert_separates, written out)
 #pragma unroll
-      for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= 0x1p-288);
+      for (int r = 0; r < 4; r++) sep |= (ha[r] - mx[r] >= CERT_SEP);
     }
     U = S.umask;
     if (S.bail || !sep || nt <= 0 || (!KEYED && nt > CHAIN_MAX)) {
@@ -908,7 +905,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
         if (p < nwin) {
 #pragma unroll
           for (int r = 0; r < 4; r++) {
-            wbad |= !(__builtin_fabs(v[u][r]) <= ZW_BIG);
+            wbad |= !cert_bounded(v[u][r]);
             S.wa[r][p] = v[u][r];
           }
           if (ud) {
@@ -1280,7 +1277,7 @@ __global__ __launch_bounds__(ZW_THREADS) void zwalk_kernel(ZwalkArgs A) {
           const double c = S.csum[a * Z + lane], bw = S.bsum[a * Z + lane];
           if (c == 0.0) ok = bw > 0.0;
           // (bw > 0: a negative bandwidth would give a negative key, ahead of every zero key)
-          else if (FF || !((U >> lane) & 1u)) ok = (c >= 0x1p-300) && (bw > 0.0) && (bw <= 0x1p300);
+          else if (FF || !((U >> lane) & 1u)) ok = (c >= CERT_C_MIN) && (bw > 0.0) && (bw <= CERT_BW_MAX);
         }
         if (__ballot(!ok)) { failed = true; break; }
         const uint32_t am = KEYED ? ~0u : S.amask[a];   // keyed: every prefix host is zero-key

@@ -3,6 +3,9 @@ exists for. A hand-over case is one in which the reference puts A's first task o
 (so an engine that ignored the failing clause would place it elsewhere); a proven case one in which
 the reference ignores the planted host although every clause sits at its limit. A later edit to
 synthetic.py or to a builder cannot silently turn a discriminating case into a vacuous one."""
+import os
+import re
+
 import numpy as np
 import pytest
 
@@ -121,3 +124,43 @@ def test_first_fit_sizes_and_keys():
     r, e, ref = cc.reference("ff_negative_demand")
     assert (r.dem < 0).sum() == 1 and r.dem[2, e.a0] == -1.0
     assert (np.sqrt((r.avail * r.avail).sum(axis=0)) > 0).all()
+
+
+def test_fixtures_sit_at_the_header_constants():
+    """The thresholds of csrc/pvt_cert.h, read from its `constexpr double NAME = 0x1p...;` lines, are
+    the values the cases are planted at: the limit itself where a case must hold, one step (a factor
+    of two) past it where it must fail."""
+    path = os.path.join(os.path.dirname(os.path.abspath(cc.synthetic.__file__)), "..", "csrc", "pvt_cert.h")
+    with open(path) as f:
+        K = {n: float.fromhex(v) for n, v in
+             re.findall(r"^constexpr\s+double\s+(\w+)\s*=\s*(0x1p[-+]?\d+)\s*;", f.read(), re.M)}
+    assert sorted(K) == ["CERT_BOUND", "CERT_BW_MAX", "CERT_C_MIN", "CERT_FF_CAP", "CERT_MARGIN",
+                         "CERT_RES_MIN", "CERT_S2_MIN", "CERT_SEP"], sorted(K)
+    assert K["CERT_S2_MIN"] == K["CERT_RES_MIN"] ** 2 and K["CERT_MARGIN"] == 2 * K["CERT_SEP"]
+
+    def clause2(name):
+        r = cc.reference(name)[0]
+        z = r.zone[cc.PLANTED]
+        return (_sum(r.cost, cc.A_ZONE, z), _sum(r.bw, cc.A_ZONE, z),
+                (r.avail.min(axis=1) - r.dem.max(axis=1)).max())
+
+    # *_at_limits: every clause that holds, holds with equality; sep_fails: c and bw likewise
+    assert clause2("all_at_limits") == (K["CERT_C_MIN"], K["CERT_BW_MAX"], K["CERT_SEP"])
+    c, bw, sep = clause2("c_at_limits")
+    assert c < K["CERT_C_MIN"] and (bw, sep) == (K["CERT_BW_MAX"], K["CERT_SEP"])
+    c, bw, sep = clause2("sep_fails")
+    assert (c, bw) == (K["CERT_C_MIN"], K["CERT_BW_MAX"]) and sep < K["CERT_SEP"]
+    # the verdict's minimum: accepted at the margin, refused one step below, where the walk's
+    # separation still holds
+    for name, v in (("verdict_min_at_limit", K["CERT_MARGIN"]), ("verdict_min_below", K["CERT_MARGIN"] / 2)):
+        r = cc.reference(name)[0]
+        assert r.avail[2].min() == r.avail[2].max() == v and v >= K["CERT_SEP"]
+    # certificate 3: one step past the bound, in a window capacity and in a demand
+    assert cc.reference("window_cap_2p501")[0].avail[0, cc.A_HOST] == 2 * K["CERT_BOUND"]
+    assert cc.reference("dem_2p501")[0].dem.max() == 2 * K["CERT_BOUND"]
+    # first-fit: the planted host's norm at the capacity bound (its capacities inside it), and a
+    # capacity past it that certificate 3 still admits
+    a = cc.reference("ff_cap_inside")[0].avail[:, cc.PLANTED]
+    assert a.max() <= K["CERT_FF_CAP"] and np.sqrt((a * a).sum()) == K["CERT_FF_CAP"]
+    a = cc.reference("ff_cap_2p500")[0].avail[:, cc.PLANTED]
+    assert K["CERT_FF_CAP"] < a.min() == a.max() <= K["CERT_BOUND"]
