@@ -541,6 +541,107 @@ typedef struct pvt_host_ops {
 int  pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* ops);
 
 /*
+ * Metering the resident cluster: the reference Meter's host half (Meter.host_check_in,
+ * resources/meter.py:59-69, Meter.host_check_out, :71-81, and _track_resource_usage, :181-187)
+ * run from the op log, on the levels the device already holds. The log of pvt_host_ops gains a
+ * time per entry, op_time[k], and two kinds: 2 = check-in and 3 = check-out of op_host[k] at
+ * op_time[k] (the amounts of a mark are ignored). Kinds 0 and 1 are as in pvt_host_ops_apply.
+ * Entries of one host apply in log order; hosts are independent.
+ *
+ * Per host the meter state is the last element of Meter.__hosts[h]: st_word[h] = 0 none,
+ * 1 open(start), 2 closed(start, end), with st_start[h] and st_end[h] (0 where not defined). A
+ * mark first records usage -- frac_r = (capacity_r - level_r) / capacity_r, one fp64 subtraction
+ * and one division, at the levels as they stand at that point of the host's log -- into the
+ * usage log, then runs the state machine; op_ok[k] receives the row's code:
+ *
+ *   check-in   none               open(t)                                              1
+ *              closed, t >  end   the closed interval goes to the interval log; open(t) 2
+ *              closed, t <= end   open(start) (the reference pops the end)             3
+ *              open               nothing                                              4
+ *   check-out  open               closed(start, t)                                     1
+ *              closed, t >  end   closed(start, t)                                     2
+ *              closed, t <= end   nothing                                              3
+ *              none               nothing (the reference raises, after the record)     0
+ *
+ * The two append logs are caller-owned device arrays of iv_cap and us_cap records: final
+ * intervals (iv_host, iv_start, iv_end) and usage records (us_host, us_time, and the four
+ * fractions record-major, us_frac[4 * i + r], so growing a log is a plain copy of its front).
+ * n_iv, n_us (the logs' counts) and last_time (the time of the last entry applied) are host-side
+ * in/out fields; a fresh meter has all three 0 and the per-host arrays zeroed. One host's records
+ * keep their log order in the raw logs, within a call and across calls; records of different
+ * hosts are in no particular order there (pvt_host_meter_finish orders them). Slots are taken
+ * with integer atomics; there are no floating-point atomics.
+ *
+ * pvt_host_meter_apply: PVT_EINVAL before any launch when n_iv + K > iv_cap or n_us + K > us_cap
+ * (a call appends at most K records to each; the caller grows the logs). PVT_EINVAL, naming the
+ * first offending entry in pvt_last_error and writing nothing (level, state, logs, counts, op_ok),
+ * when an entry has a host outside [0, H), a kind outside 0..3, a time that is not finite with
+ * 0 <= t < 2^52, a time below its predecessor's or (entry 0) below last_time, or a host with a
+ * capacity that is not > 0 in all four resources. Runs on the context's stream and synchronises
+ * before returning; the segment walk is timed under the name "host_meter_kernel". All array
+ * pointers are device pointers.
+ */
+typedef struct pvt_host_meter {
+  int32_t n_hosts, reserved;  /* H >= 1; must be 0                                        */
+  const double* capacity;     /* [4 * H]                                                  */
+  double* level;              /* [4 * H] in/out                                           */
+  int32_t* st_word;           /* [H] in/out                                               */
+  double* st_start;           /* [H] in/out                                               */
+  double* st_end;             /* [H] in/out                                               */
+  int64_t iv_cap, us_cap;     /* records the logs can hold                                */
+  int32_t* iv_host;           /* [iv_cap]                                                 */
+  double* iv_start;           /* [iv_cap]                                                 */
+  double* iv_end;             /* [iv_cap]                                                 */
+  int32_t* us_host;           /* [us_cap]                                                 */
+  double* us_time;            /* [us_cap]                                                 */
+  double* us_frac;            /* [4 * us_cap] record-major                                */
+  int64_t n_iv, n_us;         /* host-side in/out: records in the logs                    */
+  double last_time;           /* host-side in/out                                         */
+} pvt_host_meter;
+typedef struct pvt_host_meter_ops {
+  int32_t n_ops, reserved;    /* K >= 0; must be 0                                        */
+  const int32_t* op_host;     /* [K]                                                      */
+  const int32_t* op_kind;     /* [K] 0 subscribe, 1 unsubscribe, 2 check-in, 3 check-out  */
+  const double* op_amt;       /* [4 * K] as in pvt_host_ops                               */
+  const double* op_time;      /* [K] non-decreasing                                       */
+  int32_t* op_ok;             /* [K] out                                                  */
+} pvt_host_meter_ops;
+int  pvt_host_meter_apply(pvt_ctx* ctx, pvt_host_meter* m, const pvt_host_meter_ops* ops);
+
+/*
+ * The metered run so far in the layout pvt_meter_log and pvt_usage_log take (one scenario:
+ * host_off = {0, n_rows}). Non-destructive: it reads the meter and writes `out` only, so the
+ * caller may go on applying and finish again. Every host's last interval is taken as final; a
+ * host whose last interval is open gives PVT_EINVAL with the number of such hosts and the first
+ * in pvt_last_error (the reference's own properties raise on it), `out` then unspecified.
+ *
+ * capacity and level are not read and may be NULL here.
+ *
+ * Rows are the hosts with at least one usage record in HOST-INDEX order -- not the meter's dict
+ * order (first check-in). The series' integer outputs do not depend on the order of the rows;
+ * the means stay within the 1e-9 relative pvt_meter_usage states. Row i: host row_host[i], its
+ * intervals iv_off[i] .. iv_off[i+1] and records us_off[i] .. us_off[i+1], both in log order,
+ * with the fractions resource-major, us_frac[r * n_us + u]. The result is bit-identical from run
+ * to run and however the log was cut into calls.
+ *
+ * The caller sizes the arrays before the call from the meter's counts: n_us is exact
+ * (m->n_us), n_rows <= min(H, m->n_us), n_iv <= m->n_iv + min(H, m->n_us); the offset arrays
+ * hold one more than the row bound. The counts are returned in the struct. Runs on the context's
+ * stream and synchronises before returning. All array pointers are device pointers.
+ */
+typedef struct pvt_host_meter_out {
+  int32_t* row_host;          /* [R] out                                                  */
+  int64_t* iv_off;            /* [R+1] out                                                */
+  double* iv_start;           /* [n_iv] out                                               */
+  double* iv_end;             /* [n_iv] out                                               */
+  int64_t* us_off;            /* [R+1] out                                                */
+  double* us_time;            /* [n_us] out                                               */
+  double* us_frac;            /* [4 * n_us] out, resource-major                           */
+  int64_t n_rows, n_iv, n_us; /* host-side out                                            */
+} pvt_host_meter_out;
+int  pvt_host_meter_finish(pvt_ctx* ctx, const pvt_host_meter* m, pvt_host_meter_out* out);
+
+/*
  * Opt-in validation of a round's CONTENTS (no reference counterpart). The placement entry points
  * validate sizes, the mode and NULL pointers only and trust what the arrays hold -- zone, group
  * and anchor values index tables directly, and the kernels order keys by their bits -- so a caller

@@ -1,6 +1,7 @@
 // pvt_capi.hip — the C ABI (include/pivot_place.h): context, scratch, profiling, round checks and
 // the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter / pvt_meter_usage /
-// pvt_host_ops_apply (pvt_driver.h lists the driver's other files).
+// pvt_host_ops_apply / pvt_host_meter_apply / pvt_host_meter_finish (pvt_driver.h lists the
+// driver's other files).
 //
 // pvt_place() replaces the body of a reference policy's schedule() (scheduler/__init__.py:79-80,
 // called at :103). A round runs as:
@@ -21,6 +22,7 @@
 #include "pvt_meter.h"
 #include "pvt_usage.h"
 #include "pvt_hostops.h"
+#include "pvt_hostmeter.h"
 #include "pvt_stamps.h"
 
 int pvt::fail(pvt_ctx* c, int code, const char* fmt, ...) {
@@ -186,7 +188,8 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->bkey, &ctx->bidx, &ctx->bsa, &ctx->bstb, &ctx->btouch, &ctx->btlist,
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
                  &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->zpairs, &ctx->zcomp, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
-                 &ctx->chk_owner, &ctx->ho_key, &ctx->ho_idx, &ctx->ho_tmp, &ctx->ho_flag};
+                 &ctx->chk_owner, &ctx->ho_key, &ctx->ho_idx, &ctx->ho_tmp, &ctx->ho_flag,
+                 &ctx->hm_key, &ctx->hm_idx};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->evpool) (void)hipEventDestroy(e);
@@ -640,6 +643,156 @@ extern "C" int pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* o) {
     return fail(ctx, PVT_EINVAL, "op %u of the host op log: host %d (of %d), kind %d", first,
                 hk[0], o->n_hosts, hk[1]);
   }
+  return PVT_OK;
+}
+
+// ---------------------------------------------------------------- metered resident cluster
+// (levels: the call reads capacity and level; the finish does not)
+static bool meter_ok(const pvt_host_meter* m, bool levels) {
+  return m->n_hosts >= 1 && m->reserved == 0 && m->iv_cap >= 0 && m->us_cap >= 0 && m->n_iv >= 0 &&
+         m->n_us >= 0 && m->n_iv <= m->iv_cap && m->n_us <= m->us_cap &&
+         (!levels || (m->capacity && m->level)) && m->st_word && m->st_start && m->st_end &&
+         (!m->iv_cap || (m->iv_host && m->iv_start && m->iv_end)) &&
+         (!m->us_cap || (m->us_host && m->us_time && m->us_frac));
+}
+
+extern "C" int pvt_host_meter_apply(pvt_ctx* ctx, pvt_host_meter* m, const pvt_host_meter_ops* o) {
+  if (!ctx || !m || !o) return PVT_EINVAL;
+  if (!meter_ok(m, true)) return fail(ctx, PVT_EINVAL, "bad size or null pointer in pvt_host_meter");
+  if (o->n_ops < 0 || o->reserved != 0) return fail(ctx, PVT_EINVAL, "bad size in pvt_host_meter_ops");
+  if (o->n_ops == 0) return PVT_OK;
+  if (!o->op_host || !o->op_kind || !o->op_amt || !o->op_time || !o->op_ok)
+    return fail(ctx, PVT_EINVAL, "null pointer in pvt_host_meter_ops");
+  const size_t K = (size_t)o->n_ops;
+  if (m->n_iv + (int64_t)K > m->iv_cap || m->n_us + (int64_t)K > m->us_cap)
+    return fail(ctx, PVT_EINVAL,
+                "the meter's logs are full: %lld + %zu intervals of %lld, %lld + %zu usage records "
+                "of %lld", (long long)m->n_iv, K, (long long)m->iv_cap, (long long)m->n_us, K,
+                (long long)m->us_cap);
+  (void)hipSetDevice(ctx->device);
+  size_t tmp_bytes = 0;
+  HIPCHK(hostops_sort_temp(m->n_hosts, o->n_ops, &tmp_bytes));
+  ENSURE(ctx->ho_key, 2 * K * sizeof(uint32_t));
+  ENSURE(ctx->ho_idx, 2 * K * sizeof(int32_t));
+  ENSURE(ctx->ho_tmp, tmp_bytes);
+  ENSURE(ctx->ho_flag, 32);
+  uint32_t* bad = P<uint32_t>(ctx->ho_flag);
+  unsigned long long* cnt = reinterpret_cast<unsigned long long*>(bad + 2);
+  unsigned long long cnt_host[2] = {(unsigned long long)m->n_iv, (unsigned long long)m->n_us};
+  HIPCHK(hipMemsetAsync(bad, 0xff, sizeof(uint32_t), ctx->stream));   // HO_NO_BAD
+  HIPCHK(hipMemcpyAsync(cnt, cnt_host, sizeof(cnt_host), hipMemcpyHostToDevice, ctx->stream));
+  HostMeterArgs k{m->n_hosts, o->n_ops, m->capacity, m->level, m->st_word, m->st_start, m->st_end,
+                  m->iv_host, m->iv_start, m->iv_end, m->us_host, m->us_time, m->us_frac,
+                  o->op_host, o->op_kind, o->op_amt, o->op_time, o->op_ok, m->last_time,
+                  P<uint32_t>(ctx->ho_key), P<uint32_t>(ctx->ho_key) + K,
+                  P<int32_t>(ctx->ho_idx), P<int32_t>(ctx->ho_idx) + K, bad, cnt};
+  launch_hostmeter_keys(k, ctx->stream);
+  HIPCHK(hostmeter_sort(k.H, k.K, k.key_in, k.key_out, k.idx_in, k.idx_out, ctx->ho_tmp.p,
+                        tmp_bytes, ctx->stream));
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, 100.0 * (double)K, nullptr, "host_meter_kernel");
+    launch_hostmeter_apply(k, ctx->stream);
+  }
+  HIPCHK(hipGetLastError());
+  struct { uint32_t bad, pad; unsigned long long cnt[2]; } back;
+  HIPCHK(hipMemcpyAsync(&back, bad, sizeof(back), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (back.bad != HO_NO_BAD) {
+    const uint32_t first = back.bad;
+    int32_t hk[2] = {0, 0};
+    double t[2] = {m->last_time, 0.0};
+    HIPCHK(hipMemcpy(&hk[0], o->op_host + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&hk[1], o->op_kind + first, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&t[1], o->op_time + first, sizeof(double), hipMemcpyDeviceToHost));
+    if (first > 0)
+      HIPCHK(hipMemcpy(&t[0], o->op_time + first - 1, sizeof(double), hipMemcpyDeviceToHost));
+    return fail(ctx, PVT_EINVAL,
+                "entry %u of the metered op log: host %d (of %d), kind %d, time %.17g (after "
+                "%.17g), or a capacity of its host that is not positive", first, hk[0], m->n_hosts,
+                hk[1], t[1], t[0]);
+  }
+  m->n_iv = (int64_t)back.cnt[0];
+  m->n_us = (int64_t)back.cnt[1];
+  HIPCHK(hipMemcpy(&m->last_time, o->op_time + (K - 1), sizeof(double), hipMemcpyDeviceToHost));
+  return PVT_OK;
+}
+
+extern "C" int pvt_host_meter_finish(pvt_ctx* ctx, const pvt_host_meter* m, pvt_host_meter_out* out) {
+  if (!ctx || !m || !out) return PVT_EINVAL;
+  if (!meter_ok(m, false)) return fail(ctx, PVT_EINVAL, "bad size or null pointer in pvt_host_meter");
+  if (!out->iv_off || !out->us_off) return fail(ctx, PVT_EINVAL, "null pointer in pvt_host_meter_out");
+  const int64_t H = m->n_hosts, n_iv = m->n_iv, n_us = m->n_us;
+  const int64_t row_max = H < n_us ? H : n_us;
+  if (n_iv + H > INT32_MAX || n_us > INT32_MAX)
+    return fail(ctx, PVT_EUNSUPPORTED, "pvt_host_meter_finish: more than 2^31 - 1 records");
+  (void)hipSetDevice(ctx->device);
+  hipStream_t st = ctx->stream;
+  out->n_rows = out->n_iv = 0;
+  out->n_us = n_us;
+  if (n_us == 0) {                    // no mark yet: no state, no rows
+    HIPCHK(hipMemsetAsync(out->iv_off, 0, sizeof(int64_t), st));
+    HIPCHK(hipMemsetAsync(out->us_off, 0, sizeof(int64_t), st));
+    HIPCHK(hipStreamSynchronize(st));
+    return PVT_OK;
+  }
+  if (!out->row_host || !out->iv_start || !out->iv_end || !out->us_time || !out->us_frac)
+    return fail(ctx, PVT_EINVAL, "null pointer in pvt_host_meter_out");
+  const size_t n_ivk = (size_t)(n_iv + H), n_usk = (size_t)n_us;
+  size_t tmp_iv = 0, tmp_us = 0, tmp_scan = 0;
+  HIPCHK(hostops_sort_temp(m->n_hosts, (int32_t)n_ivk, &tmp_iv));
+  HIPCHK(hostops_sort_temp(m->n_hosts, (int32_t)n_usk, &tmp_us));
+  HIPCHK(hostmeter_scan_temp((int32_t)n_usk, &tmp_scan));
+  ENSURE(ctx->hm_key, (2 * n_ivk + 2 * n_usk) * sizeof(uint32_t));
+  ENSURE(ctx->hm_idx, (2 * n_ivk + 4 * n_usk) * sizeof(int32_t));
+  ENSURE(ctx->ho_tmp, std::max(tmp_iv, std::max(tmp_us, tmp_scan)));
+  ENSURE(ctx->ho_flag, 32);
+  uint32_t* words = P<uint32_t>(ctx->ho_flag);
+  const uint32_t words0[HM_WORDS] = {0u, 0xffffffffu, 0u, 0u};
+  HIPCHK(hipMemcpyAsync(words, words0, sizeof(words0), hipMemcpyHostToDevice, st));
+  uint32_t* key = P<uint32_t>(ctx->hm_key);
+  int32_t* idx = P<int32_t>(ctx->hm_idx);
+  HostMeterFinish f{};
+  f.H = m->n_hosts; f.n_iv = (int32_t)n_iv; f.n_us = (int32_t)n_us; f.n_ivf = 0;
+  f.st_word = m->st_word; f.st_start = m->st_start; f.st_end = m->st_end;
+  f.iv_host = m->iv_host; f.iv_start = m->iv_start; f.iv_end = m->iv_end;
+  f.us_host = m->us_host; f.us_time = m->us_time; f.us_frac = m->us_frac;
+  f.ivk_in = key; f.ivk_out = key + n_ivk;
+  f.usk_in = key + 2 * n_ivk; f.usk_out = f.usk_in + n_usk;
+  f.ivi_in = idx; f.ivi_out = idx + n_ivk;
+  f.usi_in = idx + 2 * n_ivk; f.usi_out = f.usi_in + n_usk;
+  f.head = f.usi_out + n_usk; f.row = f.head + n_usk;
+  f.words = words;
+  f.o_row_host = out->row_host; f.o_iv_off = out->iv_off; f.o_us_off = out->us_off;
+  f.o_iv_start = out->iv_start; f.o_iv_end = out->iv_end;
+  f.o_us_time = out->us_time; f.o_us_frac = out->us_frac;
+  launch_hostmeter_tail(f, st);
+  HIPCHK(hipGetLastError());
+  uint32_t w[HM_WORDS];
+  HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (w[0])
+    return fail(ctx, PVT_EINVAL, "%u host(s) with an open interval at finish, the first is host %u",
+                w[0], w[1]);
+  if ((int64_t)w[2] > row_max)        // (the caller sized its arrays for min(H, n_us) of them)
+    return fail(ctx, PVT_EINVAL, "pvt_host_meter: %u closed hosts but %lld usage records", w[2],
+                (long long)n_us);
+  f.n_ivf = f.n_iv + (int32_t)w[2];
+  if (f.n_ivf > 0) {
+    HIPCHK(hostmeter_sort(f.H, f.n_ivf, f.ivk_in, f.ivk_out, f.ivi_in, f.ivi_out, ctx->ho_tmp.p,
+                          tmp_iv, st));
+    launch_hostmeter_iv_gather(f, st);
+  }
+  launch_hostmeter_us_keys(f, st);
+  HIPCHK(hostmeter_sort(f.H, f.n_us, f.usk_in, f.usk_out, f.usi_in, f.usi_out, ctx->ho_tmp.p,
+                        tmp_us, st));
+  launch_hostmeter_heads(f, st);
+  HIPCHK(hostmeter_scan(f, ctx->ho_tmp.p, tmp_scan, st));
+  launch_hostmeter_rows(f, st);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(w, words, sizeof(w), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  out->n_rows = (int64_t)w[3];
+  out->n_iv = (int64_t)f.n_ivf;
   return PVT_OK;
 }
 

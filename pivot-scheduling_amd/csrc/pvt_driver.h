@@ -253,6 +253,8 @@ struct pvt_ctx {
   Buf chk_desc, chk_slots, chk_rep, chk_owner;
   // pvt_host_ops_apply: (host, k) keys and op indices, in and sorted out, the sort's temp, flag
   Buf ho_key, ho_idx, ho_tmp, ho_flag;
+  // pvt_host_meter_finish: the two logs' keys and indices (in, sorted out), heads and rows
+  Buf hm_key, hm_idx;
 };
 
 // A round of more than ZMAX zones takes the group epochs and the frontier walks (the wide

@@ -119,6 +119,30 @@ class pvt_host_ops(ctypes.Structure):
 
 # pvt_host_ops.op_kind
 HOST_OP_SUBSCRIBE, HOST_OP_UNSUBSCRIBE = 0, 1
+# pvt_host_meter_ops.op_kind: the two above and the meter's marks
+CHECK_IN, CHECK_OUT = 2, 3
+# pvt_host_meter.st_word
+METER_NONE, METER_OPEN, METER_CLOSED = 0, 1, 2
+
+
+class pvt_host_meter(ctypes.Structure):
+    _fields_ = [("n_hosts", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (n, ctypes.c_void_p) for n in ("capacity", "level", "st_word", "st_start", "st_end")] + [
+        ("iv_cap", ctypes.c_int64), ("us_cap", ctypes.c_int64)] + [
+        (n, ctypes.c_void_p) for n in ("iv_host", "iv_start", "iv_end", "us_host", "us_time",
+                                       "us_frac")] + [
+        ("n_iv", ctypes.c_int64), ("n_us", ctypes.c_int64), ("last_time", ctypes.c_double)]
+
+
+class pvt_host_meter_ops(ctypes.Structure):
+    _fields_ = [("n_ops", ctypes.c_int32), ("reserved", ctypes.c_int32)] + [
+        (n, ctypes.c_void_p) for n in ("op_host", "op_kind", "op_amt", "op_time", "op_ok")]
+
+
+class pvt_host_meter_out(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("row_host", "iv_off", "iv_start", "iv_end",
+                                               "us_off", "us_time", "us_frac")] + [
+        ("n_rows", ctypes.c_int64), ("n_iv", ctypes.c_int64), ("n_us", ctypes.c_int64)]
 
 
 class pvt_ca_items(ctypes.Structure):

@@ -75,6 +75,8 @@ def load_library(path=None):
         "pvt_meter": ([c_void_p, c_void_p], c_int),
         "pvt_meter_usage": ([c_void_p, c_void_p], c_int),
         "pvt_host_ops_apply": ([c_void_p, c_void_p], c_int),
+        "pvt_host_meter_apply": ([c_void_p, c_void_p, c_void_p], c_int),
+        "pvt_host_meter_finish": ([c_void_p, c_void_p, c_void_p], c_int),
         "pvt_check_round": ([c_void_p, c_void_p, ctypes.POINTER(_abi.pvt_check_report)], c_int),
         "pvt_check_batch": ([c_void_p, c_void_p, ctypes.c_int32,
                              ctypes.POINTER(_abi.pvt_check_report)], c_int),
@@ -784,6 +786,140 @@ class PlacementEngine:
         o.op_amt, o.op_ok = op_amt.data_ptr(), op_ok.data_ptr()
         self._bind_stream()
         self._check(self.lib.pvt_host_ops_apply(self.ctx, ctypes.addressof(o)))
+
+    # -- metered resident cluster (pvt_host_meter_apply / _finish; reference
+    #    resources/meter.py:59-81,181-187)
+    @staticmethod
+    def _meter_struct(m, capacity, level):
+        s = _abi.pvt_host_meter()
+        s.n_hosts, s.reserved = m.n_hosts, 0
+        s.capacity = None if capacity is None else capacity.data_ptr()
+        s.level = None if level is None else level.data_ptr()
+        for name in ("st_word", "st_start", "st_end", "iv_host", "iv_start", "iv_end", "us_host",
+                     "us_time", "us_frac"):
+            setattr(s, name, getattr(m, name).data_ptr())
+        s.iv_cap, s.us_cap = m.iv_cap, m.us_cap
+        s.n_iv, s.n_us, s.last_time = m.n_iv, m.n_us, m.last_time
+        return s
+
+    def host_meter_apply(self, m, capacity, level, op_host, op_kind, op_amt, op_time):
+        """Apply a metered log (``pivot_place.hostops.apply_meter_ops`` states the rules) to
+        ``level`` and to ``m``, a ``hostops.DeviceMeter`` whose logs can take K more records
+        each. Device tensors as for ``host_ops`` plus ``op_time`` float64 [K]. Returns
+        ``op_ok``. An invalid log raises and leaves everything as it was."""
+        torch = _torch()
+        H, K = level.numel() // 4, op_host.numel()
+        for t, dt, n in ((capacity, torch.float64, 4 * H), (level, torch.float64, 4 * H),
+                         (op_host, torch.int32, K), (op_kind, torch.int32, K),
+                         (op_amt, torch.float64, 4 * K), (op_time, torch.float64, K)):
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("host_meter_apply: a contiguous device tensor of %s with %d "
+                                 "elements expected" % (dt, n))
+        op_ok = torch.empty(K, dtype=torch.int32, device=level.device)
+        self.host_meter_apply_into(m, capacity, level, op_host, op_kind, op_amt, op_time, op_ok)
+        return op_ok
+
+    def host_meter_apply_into(self, m, capacity, level, op_host, op_kind, op_amt, op_time, op_ok):
+        """``host_meter_apply`` writing a caller's ``op_ok`` tensor (untouched by an invalid
+        log); ``m``'s counts and last time are updated from the call."""
+        if m.n_hosts != level.numel() // 4:
+            raise ValueError("host_meter_apply: the meter holds %d hosts, level %d"
+                             % (m.n_hosts, level.numel() // 4))
+        s = self._meter_struct(m, capacity, level)
+        o = _abi.pvt_host_meter_ops()
+        o.n_ops, o.reserved = op_host.numel(), 0
+        o.op_host, o.op_kind = op_host.data_ptr(), op_kind.data_ptr()
+        o.op_amt, o.op_time, o.op_ok = op_amt.data_ptr(), op_time.data_ptr(), op_ok.data_ptr()
+        self._bind_stream()
+        self._check(self.lib.pvt_host_meter_apply(self.ctx, ctypes.addressof(s),
+                                                  ctypes.addressof(o)))
+        m.n_iv, m.n_us, m.last_time = int(s.n_iv), int(s.n_us), float(s.last_time)
+
+    def host_meter_finish(self, m):
+        """The metered run so far as device tensors in the layout ``pvt_meter_log`` /
+        ``pvt_usage_log`` take: ``row_host`` (R,) int32 (hosts with a usage record, in
+        host-index order), ``iv_off`` / ``us_off`` (R+1,) int64, ``iv_start``, ``iv_end``,
+        ``us_time`` and ``us_frac`` (4 * n_us, resource-major). ``m`` is not changed. Raises
+        when a host's last interval is open."""
+        torch = _torch()
+        dev = m.st_word.device
+        rmax = min(m.n_hosts, m.n_us)
+        ivmax = m.n_iv + rmax
+        f64 = lambda n: torch.empty(max(n, 1), dtype=torch.float64, device=dev)
+        buf = {"row_host": torch.empty(max(rmax, 1), dtype=torch.int32, device=dev),
+               "iv_off": torch.empty(rmax + 1, dtype=torch.int64, device=dev),
+               "iv_start": f64(ivmax), "iv_end": f64(ivmax),
+               "us_off": torch.empty(rmax + 1, dtype=torch.int64, device=dev),
+               "us_time": f64(m.n_us), "us_frac": f64(4 * m.n_us)}
+        s = self._meter_struct(m, None, None)       # (finish reads neither capacity nor level)
+        out = _abi.pvt_host_meter_out()
+        for name, t in buf.items():
+            setattr(out, name, t.data_ptr())
+        self._bind_stream()
+        self._check(self.lib.pvt_host_meter_finish(self.ctx, ctypes.addressof(s),
+                                                   ctypes.addressof(out)))
+        R, n_iv, n_us = int(out.n_rows), int(out.n_iv), int(out.n_us)
+        return {"row_host": buf["row_host"][:R], "iv_off": buf["iv_off"][:R + 1],
+                "iv_start": buf["iv_start"][:n_iv], "iv_end": buf["iv_end"][:n_iv],
+                "us_off": buf["us_off"][:R + 1], "us_time": buf["us_time"][:n_us],
+                "us_frac": buf["us_frac"][:4 * n_us]}
+
+    def meter_usage_device(self, fin, sample_size, last_time):
+        """``meter_usage`` of one scenario whose arrays are on the device already (``fin``:
+        ``host_meter_finish``'s dict): nothing is uploaded but the three offsets of the
+        scenario. The scenario gets ``last_time // sample_size + 1`` buckets (``last_time``: the
+        meter's, which no interval or record exceeds), none without a record. Returns
+        ``meter_usage``'s dict."""
+        torch = _torch()
+        dev = fin["us_time"].device
+        s = int(sample_size)
+        R, n_iv, n_us = fin["row_host"].numel(), fin["iv_start"].numel(), fin["us_time"].numel()
+        NB = int(last_time // s) + 1 if n_us else 0
+        bucket_off = np.array([0, NB], dtype=np.int64)
+        off = torch.from_numpy(np.array([0, R, 0, NB], dtype=np.int64)).to(dev)
+        out = {"n_hosts": torch.zeros(max(NB, 1), dtype=torch.int32, device=dev),
+               "res_hosts": torch.zeros(max(NB, 1), dtype=torch.int32, device=dev),
+               "res_mean": torch.zeros(4 * max(NB, 1), dtype=torch.float64, device=dev),
+               "avg": torch.full((5,), float("nan"), dtype=torch.float64, device=dev)}
+        u = _abi.pvt_usage_log()
+        u.n_scen, u.reserved, u.sample_size = 1, 0, s
+        u.n_host_rows, u.n_iv, u.n_us, u.n_buckets = R, n_iv, n_us, NB
+        u.host_off, u.bucket_off = off.data_ptr(), off[2:].data_ptr()
+        for name in ("iv_off", "iv_start", "iv_end", "us_off", "us_time", "us_frac"):
+            t = fin[name]
+            setattr(u, name, t.data_ptr() if t.numel() else None)
+        u.n_hosts, u.res_hosts = out["n_hosts"].data_ptr(), out["res_hosts"].data_ptr()
+        u.res_mean, u.avg = out["res_mean"].data_ptr(), out["avg"].data_ptr()
+        self._bind_stream()
+        self._check(self.lib.pvt_meter_usage(self.ctx, ctypes.addressof(u)))
+        return {"bucket_off": bucket_off,
+                "n_hosts": out["n_hosts"][:NB].cpu().numpy(),
+                "res_hosts": out["res_hosts"][:NB].cpu().numpy(),
+                "res_mean": out["res_mean"][:4 * NB].cpu().numpy().reshape(4, NB),
+                "avg": out["avg"].cpu().numpy().reshape(1, 5)}
+
+    def meter_device(self, fin):
+        """``meter`` of one scenario without routes whose host intervals are on the device
+        already (``fin``: ``host_meter_finish``'s dict): ``instance_hours`` as there;
+        ``egress_cost`` and ``congestion_delay`` are 0."""
+        torch = _torch()
+        dev = fin["iv_start"].device
+        R, n_iv = fin["row_host"].numel(), fin["iv_start"].numel()
+        off = torch.from_numpy(np.array([0, R, 0, 0], dtype=np.int64)).to(dev)
+        out = torch.zeros(3, dtype=torch.float64, device=dev)
+        m = _abi.pvt_meter_log()
+        m.n_scen, m.reserved, m.n_host_rows, m.n_iv = 1, 0, R, n_iv
+        m.n_routes = m.n_pkts = m.n_tr = 0
+        m.host_off, m.iv_off = off.data_ptr(), fin["iv_off"].data_ptr()
+        m.iv_start = fin["iv_start"].data_ptr() if n_iv else None
+        m.iv_end = fin["iv_end"].data_ptr() if n_iv else None
+        m.route_off, m.pkt_off, m.tr_off = off[2:].data_ptr(), off[3:].data_ptr(), off[3:].data_ptr()
+        m.instance_hours, m.egress_cost = out.data_ptr(), out[1:].data_ptr()
+        m.congestion_delay = out[2:].data_ptr()
+        self._bind_stream()
+        self._check(self.lib.pvt_meter(self.ctx, ctypes.addressof(m)))
+        res = out.cpu().numpy()
+        return {"instance_hours": res[0:1], "egress_cost": res[1:2], "congestion_delay": res[2:3]}
 
     def restore_hosts(self, avail, avail0, hosts):
         """``avail[:, h] = avail0[:, h]`` for every h of ``hosts`` (pvt_restore_hosts): device
