@@ -238,6 +238,19 @@ int  pvt_prologue_stats(pvt_ctx* ctx, int64_t* fast_chains);
 /* Counters of the last pvt_place call: windows run and refills forced by exhausted lists. */
 int  pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills);
 /*
+ * The resident kernel instance of the context's last resident launch (pvt_place_batch, pvt_place
+ * and the host-array calls on rounds within the resident limits): the waves of a round's
+ * workgroup, the hosts per lane, whether a wide kernel ran (a round of more than 32 zones whose
+ * policy reads the zone tables), and the A/B switches as they took effect, in the bit values of
+ * PVT_RWALK (1, 2, 4, 8: the one-wave walks, cleared for batches with a round of more than 1024
+ * hosts and for wide kernels; 16, 32, 64 and the list minimum in bits 8-15: the multi-wave path).
+ * PVT_RES_WAVES (1, 2, 4 or 8; default 4) and PVT_RWALK are read at pvt_ctx_create and are for
+ * A/B runs; results are identical under every value. All zeros before the first resident
+ * launch. A NULL output is skipped.
+ */
+int  pvt_last_resident_shape(pvt_ctx* ctx, int32_t* waves, int32_t* hosts_per_lane, int32_t* wide,
+                             uint32_t* switches);
+/*
  * Host-dimension sharding (BASELINE config 5): `world` ranks (one per GPU)
  * each score a contiguous host range [host_lo, host_hi) and exchange per-task candidate
  * packages once per window; every rank then runs the same commit walk, so placements are

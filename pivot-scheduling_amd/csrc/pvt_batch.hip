@@ -13,7 +13,7 @@
 //     ONE launch, one block each, so the rounds' sequential walks run side by side on all CUs;
 //   - single rounds of the sim.py sizes (100-1000 hosts, configs 1-2) through pvt_place.
 //
-// A round runs on WAVES = 4 or 8 waves (one workgroup; HPL = hosts per lane, H <= 256 * 16).
+// A round runs on WAVES = 1, 2, 4 or 8 waves (one workgroup; HPL = hosts per lane, H <= 256 * 16).
 // Per task, cost_aware and first-fit rounds first look for the FAST winner, a 32-bit host index:
 //   first-fit by index (vbp first-fit, cost_aware first-fit without sort_hosts): the lowest-
 //     index fitting host (blocked host mapping: lane order, then slot order, is index order);
@@ -279,11 +279,19 @@ __device__ int resident_walk(const pvt_round& R, const ResLds& Lo, char* smem, c
     }
   }
   __syncthreads();
-  if (tid < 4)
-    for (int blk = nsb - 2; blk >= 0; blk--) ws[blk * 4 + tid] = fmin(ws[blk * 4 + tid], ws[(blk + 1) * 4 + tid]);
-  else if (tid >= 64 && tid < 68)
-    for (int blk = nsb - 2; blk >= 0; blk--)
-      wx[blk * 4 + tid - 64] = fmax(wx[blk * 4 + tid - 64], wx[(blk + 1) * 4 + tid - 64]);
+  // suffix minima (threads 0-3) and maxima (4-7) per dimension, from the last block down: one
+  // loop of wave 0, which every shape has (a round on one wave has no thread 64)
+  if (tid < 8) {
+    const int r = tid & 3;
+    const bool mx = tid >= 4;
+    double* s = mx ? wx : ws;
+    double acc = s[(nsb - 1) * 4 + r];
+    for (int blk = nsb - 2; blk >= 0; blk--) {
+      const double v = s[blk * 4 + r];
+      acc = mx ? fmax(v, acc) : fmin(v, acc);
+      s[blk * 4 + r] = acc;
+    }
+  }
   __syncthreads();
   if (wave == walker) {
     ResWalkStamps st;
@@ -1550,19 +1558,7 @@ static void launch_mode(int waves, int hpl, int n, size_t lds, const ResidentArg
   else launch_waves<MODE, 4>(hpl, n, lds, a, st);
 }
 
-// Waves and hosts per lane for a batch whose largest round has maxH hosts: `waves` (4 or 8) on
-// entry is the preference; 8 waves only while the round needs at most 8 hosts per lane.
-void resident_shape(int maxH, int* waves, int* hpl) {
-  // (waves 2 and 1 -- 8 and 16 hosts per lane -- only as A/B preferences, PVT_RES_WAVES)
-  const int w = (*waves == 8 && maxH <= 8 * 8 * WAVE) ? 8
-                : (*waves == 2 && maxH > 2 * 4 * WAVE && maxH <= 2 * 16 * WAVE) ? 2
-                : (*waves == 1 && maxH > 8 * WAVE && maxH <= 16 * WAVE) ? 1 : 4;
-  int h = 1;
-  while (h * w * WAVE < maxH) h <<= 1;
-  *waves = w;
-  *hpl = h;
-}
-
+// (waves, hpl): resident_shape's (pvt_kernels.h)
 void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const ResidentArgs& a,
                      hipStream_t st) {
   if (mode == RES_MIXED) {             // (four waves; resident_shape with waves = 4)

@@ -321,6 +321,15 @@ extern "C" int pvt_last_stats(pvt_ctx* ctx, int64_t* windows, int64_t* refills) 
   if (refills) *refills = ctx->refills;
   return PVT_OK;
 }
+extern "C" int pvt_last_resident_shape(pvt_ctx* ctx, int32_t* waves, int32_t* hosts_per_lane,
+                                       int32_t* wide, uint32_t* switches) {
+  if (!ctx) return PVT_EINVAL;
+  if (waves) *waves = ctx->rs_waves;
+  if (hosts_per_lane) *hosts_per_lane = ctx->rs_hpl;
+  if (wide) *wide = ctx->rs_wide;
+  if (switches) *switches = ctx->rs_switches;
+  return PVT_OK;
+}
 // Diagnostic (not part of the public ABI): commit-walk phase cycle sums of a PVT_STAMPS build.
 extern "C" int pvt_debug_commit_stamps(pvt_ctx* ctx, uint64_t* out, int n) {
   if (!ctx || !out || n < 8) return PVT_EINVAL;

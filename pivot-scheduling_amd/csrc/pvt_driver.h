@@ -203,7 +203,11 @@ struct pvt_ctx {
   int t_zw_runrem = 1;            // PVT_ZW_RUNREM: 0 = the walk finds its runs itself, 64 tasks at the most
   int t_zw_wide = 1;              // PVT_ZW_WIDE: 0 = rounds of more than ZMAX zones plan no epoch and no frontier walk
   int t_merge_bitonic = 0;        // PVT_MERGE_SMALL=0: the bitonic merge always
-  int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (2, 4 or 8)
+  int res_waves = 4;              // PVT_RES_WAVES: waves per resident round (1, 2, 4 or 8)
+  // the last resident launch (pvt_last_resident_shape): its plan's waves, hosts per lane, wide
+  // kernel, and its switches as resident_switches_word writes them; zeros before the first one
+  int rs_waves = 0, rs_hpl = 0, rs_wide = 0;
+  uint32_t rs_switches = 0;
   int rwalk = 9;                  // PVT_RWALK: the raw word (resident_switches, pvt_kernels.h, decodes it)
   int fused = 1;                  // PVT_FUSED=0: host batches staged in six launches (A/B)
   Buf bkey, bidx, bsa, bstb, btouch, btlist, btcnt, bsorttmp;   // band lists: sorted snapshot

@@ -617,6 +617,25 @@ static_assert(resident_switches(64 + (12 << 8), 1024) == ResidentSwitches{0, 0, 
               resident_switches(64 + (12 << 8), 1025) == resident_switches(64 + (12 << 8), 1024),
               "64 and the list minimum hold at every size");
 static_assert(resident_switches(2, 1024) == ResidentSwitches{1, 0, 1, 1, 1, 1, 0, 0}, "2: rotated walker");
+// The switches as they took effect, in the PVT_RWALK bit values above (pvt_last_resident_shape):
+// the word that decodes to `s`, with 3 written as 1 and no walk bit where nothing is walked.
+constexpr uint32_t resident_switches_word(const ResidentSwitches& s) {
+  return (s.walk_rotate ? 2u : s.walk_ca_bf ? 1u : 0u) | (s.walk_ff ? 8u : 0u) |
+         (s.walks() && !s.walk_bulk ? 4u : 0u) | (s.bulk_sticky ? 0u : 16u) | (s.run_lists ? 0u : 32u) |
+         (s.lists_all ? 64u : 0u) | ((uint32_t)s.list_min << 8);
+}
+static_assert(resident_switches_word(resident_switches(9, 1024)) == 9 &&
+              resident_switches_word(resident_switches(9, 1025)) == 0, "the default; no walk above RW_MAXH");
+static_assert(resident_switches_word(resident_switches(3, 1024)) == 1 &&
+              resident_switches_word(resident_switches(10, 1024)) == 10 &&
+              resident_switches_word(resident_switches(13, 1024)) == 13 &&
+              resident_switches_word(resident_switches(13, 1025)) == 0, "the walk bits");
+static_assert(resident_switches_word(resident_switches(73, 1024)) == 73 &&
+              resident_switches_word(resident_switches(585, 1024)) == 585 &&
+              resident_switches_word(resident_switches(585, 1025)) == 576 &&
+              resident_switches_word(resident_switches(48, 4096)) == 48, "the 4-wave bits at every size");
+static_assert(resident_switches(resident_switches_word(resident_switches(0x1f7f, 1024)), 1024) ==
+              resident_switches(0x1f7f, 1024), "the word decodes to the same switches");
 struct ResidentArgs {
   const void* rounds;     // device copy of pvt_round[n] (device array pointers)
   uint32_t* mt;           // [n][625] MT19937 states (PVT_OPP; the kernel uses R.mt_state)
@@ -626,7 +645,40 @@ struct ResidentArgs {
   ResidentSwitches sw;
 };
 size_t resident_lds_bytes(int Zb, int Tpad, const ResidentSwitches& sw);
-void resident_shape(int maxH, int* waves, int* hpl);
+// Waves and hosts per lane of a batch whose largest round has maxH hosts. `pref` is the preferred
+// number of waves: 4 (the default) or, as A/B preferences (PVT_RES_WAVES), 8 -- every resident
+// size, at most 8 hosts per lane -- , 2 -- rounds of 513 to 2048 hosts, 8 or 16 hosts per lane --
+// and 1 -- rounds of 513 to 1024 hosts, 16 hosts per lane; outside those sizes four waves.
+struct ResidentShape {
+  int waves, hpl;
+};
+constexpr ResidentShape resident_shape(int pref, int maxH) {
+  const int w = (pref == 8 && maxH <= 8 * 8 * WAVE) ? 8
+                : (pref == 2 && maxH > 2 * 4 * WAVE && maxH <= 2 * 16 * WAVE) ? 2
+                : (pref == 1 && maxH > 8 * WAVE && maxH <= 16 * WAVE) ? 1 : 4;
+  int h = 1;
+  while (h * w * WAVE < maxH) h <<= 1;
+  return ResidentShape{w, h};
+}
+constexpr bool operator==(const ResidentShape& a, const ResidentShape& b) {
+  return a.waves == b.waves && a.hpl == b.hpl;
+}
+static_assert(resident_shape(4, 1) == ResidentShape{4, 1} && resident_shape(4, 256) == ResidentShape{4, 1} &&
+              resident_shape(4, 257) == ResidentShape{4, 2} && resident_shape(4, 1024) == ResidentShape{4, 4} &&
+              resident_shape(4, 1025) == ResidentShape{4, 8} && resident_shape(4, 2049) == ResidentShape{4, 16} &&
+              resident_shape(4, RES_MAX_HOSTS) == ResidentShape{4, 16}, "the default: four waves");
+static_assert(resident_shape(8, 1) == ResidentShape{8, 1} && resident_shape(8, 65) == ResidentShape{8, 1} &&
+              resident_shape(8, 512) == ResidentShape{8, 1} && resident_shape(8, 513) == ResidentShape{8, 2} &&
+              resident_shape(8, 1024) == ResidentShape{8, 2} && resident_shape(8, 1025) == ResidentShape{8, 4} &&
+              resident_shape(8, 2048) == ResidentShape{8, 4} && resident_shape(8, 2049) == ResidentShape{8, 8} &&
+              resident_shape(8, RES_MAX_HOSTS) == ResidentShape{8, 8}, "8: eight waves at every resident size");
+static_assert(resident_shape(2, 512) == ResidentShape{4, 2} && resident_shape(2, 513) == ResidentShape{2, 8} &&
+              resident_shape(2, 1024) == ResidentShape{2, 8} && resident_shape(2, 1025) == ResidentShape{2, 16} &&
+              resident_shape(2, 2048) == ResidentShape{2, 16} && resident_shape(2, 2049) == ResidentShape{4, 16},
+              "2: two waves for 513 to 2048 hosts, four outside");
+static_assert(resident_shape(1, 512) == ResidentShape{4, 2} && resident_shape(1, 513) == ResidentShape{1, 16} &&
+              resident_shape(1, 1024) == ResidentShape{1, 16} && resident_shape(1, 1025) == ResidentShape{4, 8},
+              "1: one wave for 513 to 1024 hosts, four outside");
 // lds: resident_lds_bytes of (a.Zb, a.Tpad, a.sw) at least
 void launch_resident(int mode, int waves, int hpl, int n, size_t lds, const ResidentArgs& a,
                      hipStream_t st);

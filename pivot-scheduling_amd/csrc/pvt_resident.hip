@@ -60,8 +60,9 @@ static ResidentPlan plan_resident(const pvt_ctx* ctx, const pvt_round* rounds, c
     plan.cand += c;
     plan.bytes += c * bytes_per_candidate(r.mode);
   }
-  plan.waves = waves;
-  resident_shape(maxH, &plan.waves, &plan.hpl);
+  const ResidentShape shape = resident_shape(waves, maxH);
+  plan.waves = shape.waves;
+  plan.hpl = shape.hpl;
   while (plan.Tpad < maxT) plan.Tpad <<= 1;
   plan.sw = resident_switches(ctx->rwalk, maxH);
   if (plan.Zb > ZMAX) {
@@ -69,7 +70,7 @@ static ResidentPlan plan_resident(const pvt_ctx* ctx, const pvt_round* rounds, c
     plan.wide_kernel = tables || mixed;
     if (plan.wide_kernel) {       // four waves, no one-wave walks (32-bit zone masks)
       plan.waves = 4;
-      resident_shape(maxH, &plan.waves, &plan.hpl);
+      plan.hpl = resident_shape(4, maxH).hpl;
       plan.sw.walk_ca_bf = plan.sw.walk_ff = plan.sw.walk_rotate = plan.sw.walk_bulk = 0;
     }
   }
@@ -84,6 +85,14 @@ static int plan_check(pvt_ctx* ctx, const ResidentPlan& plan) {
     return fail(ctx, PVT_EUNSUPPORTED, "a batch with a round of more than %d zones takes rounds of at most "
                 "%d hosts: place the larger rounds in a batch of their own", ZMAX, RES_WIDE_MAX_HOSTS);
   return PVT_OK;
+}
+
+// What pvt_last_resident_shape reports: the plan of the launch just made.
+static void plan_launched(pvt_ctx* ctx, const ResidentPlan& plan) {
+  ctx->rs_waves = plan.waves;
+  ctx->rs_hpl = plan.hpl;
+  ctx->rs_wide = plan.wide_kernel ? 1 : 0;
+  ctx->rs_switches = resident_switches_word(plan.sw);
 }
 
 static ResidentArgs plan_args(const pvt_ctx* ctx, const ResidentPlan& plan, const void* desc, uint32_t* mt) {
@@ -103,6 +112,7 @@ static int run_resident(pvt_ctx* ctx, const ResidentPlan& plan, int mode, const 
                       ctx->stream);
   }
   HIPCHK(hipGetLastError());
+  plan_launched(ctx, plan);
   ctx->windows = plan.n;
   ctx->refills = 0;
   return PVT_OK;
@@ -539,6 +549,7 @@ static int place_host_fused(pvt_ctx* ctx, const HostBatch& B) {
     else launch_fused(B.mode, plan.hpl, plan.n, plan.lds, F, ctx->stream);
   }
   HIPCHK(hipGetLastError());
+  plan_launched(ctx, plan);
   ctx->windows = plan.n;
   ctx->refills = 0;
   return PVT_OK;

@@ -63,6 +63,8 @@ def load_library(path=None):
         "pvt_prologue_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64)], c_int),
         "pvt_last_stats": ([c_void_p, ctypes.POINTER(ctypes.c_int64),
                             ctypes.POINTER(ctypes.c_int64)], c_int),
+        "pvt_last_resident_shape": ([c_void_p] + [ctypes.POINTER(ctypes.c_int32)] * 3 +
+                                    [ctypes.POINTER(ctypes.c_uint32)], c_int),
         "pvt_last_error": ([c_void_p], ctypes.c_char_p),
         "pvt_shard_begin": ([c_void_p, c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                              ctypes.POINTER(ctypes.c_int64)], c_int),
@@ -1048,6 +1050,17 @@ class PlacementEngine:
         w, r = ctypes.c_int64(), ctypes.c_int64()
         self._check(self.lib.pvt_last_stats(self.ctx, ctypes.byref(w), ctypes.byref(r)))
         return {"windows": w.value, "refills": r.value}
+
+    def resident_shape(self):
+        """The resident kernel instance of this engine's last resident launch
+        (pvt_last_resident_shape): waves per round, hosts per lane, whether a wide kernel ran,
+        and the PVT_RWALK switches as they took effect. Zeros before the first such launch."""
+        w, h, wide = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        sw = ctypes.c_uint32()
+        self._check(self.lib.pvt_last_resident_shape(self.ctx, ctypes.byref(w), ctypes.byref(h),
+                                                     ctypes.byref(wide), ctypes.byref(sw)))
+        return {"waves": w.value, "hosts_per_lane": h.value, "wide": wide.value,
+                "switches": sw.value}
 
 
 _engines = {}

@@ -63,6 +63,9 @@ def test_null_arguments_are_rejected_without_a_device():
     assert lib.pvt_place(None, None) == _abi.PVT_EINVAL
     assert lib.pvt_ctx_destroy(None) == _abi.PVT_EINVAL
     assert lib.pvt_ctx_create(0, None) == _abi.PVT_EINVAL
+    w = ctypes.c_int32(7)
+    assert lib.pvt_last_resident_shape(None, ctypes.byref(w), None, None, None) == _abi.PVT_EINVAL
+    assert w.value == 7                      # (nothing is written without a context)
 
 
 def test_no_device_means_enodev():

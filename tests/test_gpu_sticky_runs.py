@@ -18,6 +18,8 @@ from oracle import oracle
 from pivot_place import _abi, synthetic
 from pivot_place.engine import PlacementEngine
 
+from resident_shape_cases import edit as _edit   # (the demand edits, shared with the shape cases)
+
 pytestmark = pytest.mark.gpu
 
 MODES = [(_abi.PVT_CA_FF, True), (_abi.PVT_CA_FF, False), (_abi.PVT_CA_BF, True),
@@ -57,30 +59,6 @@ def _check(engines, rounds, what):
         ref = oracle.place(r)
         _same(g, ref, "%s round %d (bulk sticky)" % (what, i))
         _same(b, ref, "%s round %d (per-task sticky)" % (what, i))
-
-
-def _edit(r, rs, s):
-    """The demand edit `s` of test_sticky_runs_match_oracle on round r."""
-    if s == 0:                               # two rows only: runs of hundreds of tasks
-        rows = np.array([[0.5, 2048.0], [0.25, 1024.0]])
-        pick = rs.randint(0, 2, size=r.n_tasks)
-        r.dem[0], r.dem[1] = rows[pick, 0], rows[pick, 1]
-    elif s == 1:                             # not exactly representable, tight hosts
-        r.dem[0] = 0.1
-        r.dem[1] = 0.3 * 1024.0
-        r.avail[0] = 0.1 * rs.randint(1, 30, size=r.n_hosts) + 0.05 * (s % 2)
-    elif s == 2:                             # all-zero rows between the others
-        r.dem[:, ::3] = 0.0
-    elif s == 3:                             # one row, few hosts: winners run out mid-run
-        r.dem[0], r.dem[1] = 1.5, 3000.0
-        r.avail[0] = np.minimum(r.avail[0], 4.5)
-    elif s == 4:                             # exact fits (strict modes: the last copy fails)
-        r.dem[0], r.dem[1] = 0.5, 2048.0
-        r.avail[0] = 0.5 * rs.randint(0, 6, size=r.n_hosts)
-        r.avail[1] = 2048.0 * rs.randint(0, 6, size=r.n_hosts)
-    else:                                    # fewer distinct rows: longer runs
-        r.dem[0] = np.round(r.dem[0] * 4) / 4
-        r.dem[1] = np.round(r.dem[1] / 4096.0) * 4096.0
 
 
 @pytest.mark.parametrize("mode,sort_hosts", MODES)
