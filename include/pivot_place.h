@@ -179,7 +179,8 @@ int  pvt_get_kstats(pvt_ctx* ctx, int kclass, pvt_kstats* out);
  * "opp_count_kernel", "score_kernel", "band_score_kernel", "perm_scan_kernel", "ordered_kernel",
  * "resident_kernel", "merge_kernel", "merge_small_kernel", "merge_pkg_kernel",
  * "merge_path_kernel"; "check_kernel" of pvt_check_round / pvt_set_checks; and
- * "host_ops_kernel", the segment walk of pvt_host_ops_apply), each bracketed
+ * "host_ops_kernel", the segment walk of pvt_host_ops_apply, and "rt_fill_kernel", the
+ * streaming pass of pvt_rt_rows), each bracketed
  * by its own HIP events on the stream it runs on. An unknown or unlaunched name gives zeros. */
 int  pvt_get_kernel_kstats(pvt_ctx* ctx, const char* kernel, pvt_kstats* out);
 /* With profiling on = 2, record events around the launches of this one named kernel only
@@ -552,6 +553,58 @@ typedef struct pvt_host_ops {
   int32_t* op_ok;             /* [K] out                                                  */
 } pvt_host_ops;
 int  pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* ops);
+
+/*
+ * Realtime-bandwidth rows built on the device: pvt_round.rt_bw of a cost_aware round with
+ * realtime_bw (scheduler/cost_aware.py:73-79,106-112) from the zone table and a sparse list of
+ * route queues, so that a resident cluster uploads O(listed routes + packets) bytes per round
+ * and no dense [G*H] array.
+ *
+ * The rule (resources/network.py:70-73): a route's realtime bandwidth is
+ *     est = (Q + 1) / bw;   est ? 1 / est : bw
+ * with Q the sum of its queued packets' MB, added left to right in queue order, from 0, in fp64
+ * (the sum depends on the order, and _transfer rotates the queue, :99-100), and bw the route's
+ * own bandwidth. Both divisions are performed: an idle route's value is 1 / (1 / bw), which is
+ * not bw for about one bw in nine. A NaN est takes the division, as in Python.
+ *
+ *     rt_bw[g*H + h] = in + out      (in that order), a = group_anchor[g]
+ *     in   the value of the listed route (a, h, dir 0: storage -> host, the reference's in_route),
+ *          or of an empty queue on bw[a*Z + zone[h]] when it is not listed
+ *     out  likewise for (a, h, dir 1: host -> storage, out_route) and bw[zone[h]*Z + a]
+ * G = 0 (group_anchor ignored) gives the one row of zone 0, pvt_round.rt_bw's convention for a
+ * round without task_group. Groups that share an anchor get equal rows; an entry whose anchor
+ * is no group's is checked and stores nothing.
+ *
+ * The list: R entries sorted by (rq_anchor, rq_host, rq_dir), strictly ascending (no
+ * duplicates), with 0 <= rq_anchor < Z, 0 <= rq_host < H, rq_dir 0 or 1, rq_bw > 0 (NaN fails;
+ * the reference raises on 0); entry i's packets are rq_mbs[rq_off[i] .. rq_off[i+1]), each > 0
+ * (NaN fails; Packet.__init__ asserts it), with rq_off[0] = 0, rq_off non-decreasing and
+ * rq_off[R] = n_packets. An entry without packets is legal (a route replaced by one of another
+ * bandwidth). Infinite values are allowed and follow IEEE. group_anchor[g] and zone[h] lie in
+ * [0, Z).
+ *
+ * PVT_EINVAL, with rt_bw untouched, when the list breaks the contract (pvt_last_error names the
+ * first such entry), or a group_anchor[g] or a zone[h] is out of range. R = 0 fills idle rows
+ * only. IEEE divisions, no contraction, no floating-point atomics: equal bits on every call.
+ * Runs on the context's stream and synchronises before returning. All pointers are device
+ * pointers. The pass that streams the rows is timed under the name "rt_fill_kernel"
+ * (pvt_get_kernel_kstats; its bytes: G*H*8 written + ceil(G/8)*H*4 read).
+ */
+typedef struct pvt_route_queues {
+  int32_t n_hosts, n_zones, n_groups, n_routes;  /* H >= 1, 1 <= Z <= PVT_MAX_ZONES, G >= 0 (0: one row, zone 0), R >= 0 */
+  const int32_t* zone;          /* [H]            */
+  const double*  bw;            /* [Z*Z]          */
+  const int32_t* group_anchor;  /* [G] or NULL    */
+  const int32_t* rq_anchor;     /* [R]            */
+  const int32_t* rq_host;       /* [R]            */
+  const int32_t* rq_dir;        /* [R]            */
+  const double*  rq_bw;         /* [R]            */
+  const int64_t* rq_off;        /* [R+1]          */
+  const double*  rq_mbs;        /* [rq_off[R]]    */
+  int64_t n_packets;            /* P, the caller's count: rq_off[R] must equal it */
+  double* rt_bw;                /* [max(G,1)*H] out */
+} pvt_route_queues;
+int  pvt_rt_rows(pvt_ctx* ctx, const pvt_route_queues* q);
 
 /*
  * Metering the resident cluster: the reference Meter's host half (Meter.host_check_in,

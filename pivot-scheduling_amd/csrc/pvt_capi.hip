@@ -1,6 +1,6 @@
 // pvt_capi.hip — the C ABI (include/pivot_place.h): context, scratch, profiling, round checks and
 // the entry points pvt_place / pvt_place_batch / pvt_anchor / pvt_meter / pvt_meter_usage /
-// pvt_host_ops_apply / pvt_host_meter_apply / pvt_host_meter_finish (pvt_driver.h lists the
+// pvt_host_ops_apply / pvt_host_meter_apply / pvt_host_meter_finish / pvt_rt_rows (pvt_driver.h lists the
 // driver's other files).
 //
 // pvt_place() replaces the body of a reference policy's schedule() (scheduler/__init__.py:79-80,
@@ -23,6 +23,7 @@
 #include "pvt_usage.h"
 #include "pvt_hostops.h"
 #include "pvt_hostmeter.h"
+#include "pvt_rtrows.h"
 #include "pvt_stamps.h"
 
 int pvt::fail(pvt_ctx* c, int code, const char* fmt, ...) {
@@ -189,7 +190,7 @@ extern "C" int pvt_ctx_destroy(pvt_ctx* ctx) {
                  &ctx->btcnt, &ctx->bsorttmp, &ctx->brun, &ctx->brdem, &ctx->bpos, &ctx->bptouch, &ctx->zt_dev,
                  &ctx->zwin, &ctx->zundo, &ctx->gcert, &ctx->run_rem, &ctx->zpairs, &ctx->zcomp, &ctx->brec, &ctx->chk_desc, &ctx->chk_slots, &ctx->chk_rep,
                  &ctx->chk_owner, &ctx->ho_key, &ctx->ho_idx, &ctx->ho_tmp, &ctx->ho_flag,
-                 &ctx->hm_key, &ctx->hm_idx};
+                 &ctx->hm_key, &ctx->hm_idx, &ctx->rt_val, &ctx->rt_flag};
   for (Buf* b : bufs)
     if (b->p) (void)hipFree(b->p);
   for (hipEvent_t e : ctx->evpool) (void)hipEventDestroy(e);
@@ -651,6 +652,76 @@ extern "C" int pvt_host_ops_apply(pvt_ctx* ctx, const pvt_host_ops* o) {
     HIPCHK(hipMemcpy(&hk[1], o->op_kind + first, sizeof(int32_t), hipMemcpyDeviceToHost));
     return fail(ctx, PVT_EINVAL, "op %u of the host op log: host %d (of %d), kind %d", first,
                 hk[0], o->n_hosts, hk[1]);
+  }
+  return PVT_OK;
+}
+
+// ---------------------------------------------------------------- realtime-bandwidth rows
+extern "C" int pvt_rt_rows(pvt_ctx* ctx, const pvt_route_queues* q) {
+  if (!ctx || !q) return PVT_EINVAL;
+  if (q->n_hosts < 1 || q->n_zones < 1 || q->n_zones > PVT_MAX_ZONES || q->n_groups < 0 ||
+      q->n_routes < 0 || q->n_packets < 0)
+    return fail(ctx, PVT_EINVAL, "bad size in pvt_route_queues: H=%d Z=%d (1 <= Z <= %d) G=%d R=%d P=%lld",
+                q->n_hosts, q->n_zones, PVT_MAX_ZONES, q->n_groups, q->n_routes, (long long)q->n_packets);
+  const int rows = q->n_groups > 0 ? q->n_groups : 1;
+  if ((rows + RT_GROUPS - 1) / RT_GROUPS > 65535)
+    return fail(ctx, PVT_EINVAL, "pvt_route_queues: %d groups (at most %d)", q->n_groups, 65535 * RT_GROUPS);
+  if (!q->zone || !q->bw || !q->rt_bw || (q->n_groups > 0 && !q->group_anchor))
+    return fail(ctx, PVT_EINVAL, "null pointer in pvt_route_queues");
+  if (q->n_routes > 0 && (!q->rq_anchor || !q->rq_host || !q->rq_dir || !q->rq_bw || !q->rq_off))
+    return fail(ctx, PVT_EINVAL, "null route array in pvt_route_queues");
+  if (q->n_packets > 0 && (!q->rq_mbs || q->n_routes == 0))
+    return fail(ctx, PVT_EINVAL, "pvt_route_queues: %lld packets of %d routes, rq_mbs %s",
+                (long long)q->n_packets, q->n_routes, q->rq_mbs ? "set" : "NULL");
+  if ((uintptr_t)q->rt_bw % sizeof(double))
+    return fail(ctx, PVT_EINVAL, "pvt_route_queues: rt_bw is not aligned to 8 bytes");
+  (void)hipSetDevice(ctx->device);
+  const size_t R = (size_t)q->n_routes;
+  ENSURE(ctx->rt_val, R * sizeof(double));
+  ENSURE(ctx->rt_flag, 16);
+  uint32_t* bad = P<uint32_t>(ctx->rt_flag);
+  HIPCHK(hipMemsetAsync(bad, 0xff, 4 * sizeof(uint32_t), ctx->stream));   // RT_NO_BAD
+  RtRowsArgs a{q->n_hosts, q->n_zones, q->n_groups, q->n_routes, q->n_packets, q->zone, q->bw,
+               q->group_anchor, q->rq_anchor, q->rq_host, q->rq_dir, q->rq_bw, q->rq_off, q->rq_mbs,
+               P<double>(ctx->rt_val), q->rt_bw, bad};
+  launch_rt_check(a, ctx->stream);
+  launch_rt_value(a, ctx->stream);
+  {
+    Scope sc(ctx, PVT_K_OTHER, 0, rtrows_fill_bytes(a), nullptr, "rt_fill_kernel");
+    launch_rt_fill(a, ctx->stream);
+  }
+  launch_rt_patch(a, ctx->stream);
+  HIPCHK(hipGetLastError());
+  uint32_t first[3] = {RT_NO_BAD, RT_NO_BAD, RT_NO_BAD};
+  HIPCHK(hipMemcpyAsync(first, bad, sizeof(first), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  if (first[0] != RT_NO_BAD) {
+    const uint32_t i = first[0];
+    int32_t k[3] = {0, 0, 0};
+    int64_t off[2] = {0, 0};
+    double b = 0.0;
+    HIPCHK(hipMemcpy(&k[0], q->rq_anchor + i, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&k[1], q->rq_host + i, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&k[2], q->rq_dir + i, sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&b, q->rq_bw + i, sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(off, q->rq_off + i, 2 * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return fail(ctx, PVT_EINVAL,
+                "entry %u of the route queues: anchor %d (of %d), host %d (of %d), dir %d, bw %.17g, "
+                "packets [%lld, %lld) of %lld (keys ascend strictly, bw and packets are > 0)",
+                i, k[0], q->n_zones, k[1], q->n_hosts, k[2], b, (long long)off[0], (long long)off[1],
+                (long long)q->n_packets);
+  }
+  if (first[1] != RT_NO_BAD) {
+    int32_t an = 0;
+    HIPCHK(hipMemcpy(&an, q->group_anchor + first[1], sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(ctx, PVT_EINVAL, "group_anchor[%u] = %d of the route queues' round (of %d zones)",
+                first[1], an, q->n_zones);
+  }
+  if (first[2] != RT_NO_BAD) {
+    int32_t z = 0;
+    HIPCHK(hipMemcpy(&z, q->zone + first[2], sizeof(int32_t), hipMemcpyDeviceToHost));
+    return fail(ctx, PVT_EINVAL, "zone[%u] = %d of the route queues' cluster (of %d zones)", first[2],
+                z, q->n_zones);
   }
   return PVT_OK;
 }

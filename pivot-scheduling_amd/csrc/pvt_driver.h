@@ -259,6 +259,8 @@ struct pvt_ctx {
   Buf ho_key, ho_idx, ho_tmp, ho_flag;
   // pvt_host_meter_finish: the two logs' keys and indices (in, sorted out), heads and rows
   Buf hm_key, hm_idx;
+  // pvt_rt_rows: the listed routes' realtime bandwidths, the three verdict words
+  Buf rt_val, rt_flag;
 };
 
 // A round of more than ZMAX zones takes the group epochs and the frontier walks (the wide

@@ -117,6 +117,13 @@ class pvt_host_ops(ctypes.Structure):
                                        "op_ok")]
 
 
+class pvt_route_queues(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("n_hosts", "n_zones", "n_groups", "n_routes")] + [
+        (n, ctypes.c_void_p) for n in ("zone", "bw", "group_anchor", "rq_anchor", "rq_host",
+                                       "rq_dir", "rq_bw", "rq_off", "rq_mbs")] + [
+        ("n_packets", ctypes.c_int64), ("rt_bw", ctypes.c_void_p)]
+
+
 # pvt_host_ops.op_kind
 HOST_OP_SUBSCRIBE, HOST_OP_UNSUBSCRIBE = 0, 1
 # pvt_host_meter_ops.op_kind: the two above and the meter's marks

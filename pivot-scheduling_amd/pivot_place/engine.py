@@ -77,6 +77,7 @@ def load_library(path=None):
         "pvt_meter": ([c_void_p, c_void_p], c_int),
         "pvt_meter_usage": ([c_void_p, c_void_p], c_int),
         "pvt_host_ops_apply": ([c_void_p, c_void_p], c_int),
+        "pvt_rt_rows": ([c_void_p, c_void_p], c_int),
         "pvt_host_meter_apply": ([c_void_p, c_void_p, c_void_p], c_int),
         "pvt_host_meter_finish": ([c_void_p, c_void_p, c_void_p], c_int),
         "pvt_check_round": ([c_void_p, c_void_p, ctypes.POINTER(_abi.pvt_check_report)], c_int),
@@ -788,6 +789,56 @@ class PlacementEngine:
         o.op_amt, o.op_ok = op_amt.data_ptr(), op_ok.data_ptr()
         self._bind_stream()
         self._check(self.lib.pvt_host_ops_apply(self.ctx, ctypes.addressof(o)))
+
+    # -- realtime-bandwidth rows from route queues (pvt_rt_rows; reference
+    #    resources/network.py:70-73, scheduler/cost_aware.py:73-79)
+    def rt_rows(self, zone, bw, group_anchor, rq, out=None):
+        """The rows of ``pvt_round.rt_bw`` built on the device (``pivot_place.routes.realtime_rows``
+        states the rule in Python). Device tensors: ``zone`` int32 [H], ``bw`` float64 [Z*Z],
+        ``group_anchor`` int32 [G] or None (one row, anchored at zone 0), and ``rq`` an object
+        with the six arrays of a ``RouteQueues`` as device tensors (``anchor``, ``host``, ``dir``
+        int32 [R], ``bw`` float64 [R], ``off`` int64 [R+1], ``mbs`` float64 [P]), or None for no
+        listed route. Returns a float64 device tensor (max(G,1), H): ``out`` when given (a
+        contiguous float64 device tensor with at least that many elements; its first max(G,1)*H
+        are written), else a new one. A list that breaks the contract raises and writes nothing."""
+        torch = _torch()
+        H = zone.numel()
+        Z = int(round(bw.numel() ** 0.5))
+        G = 0 if group_anchor is None else group_anchor.numel()
+        rows = max(G, 1)
+        names = ("anchor", "host", "dir", "bw", "off", "mbs")
+        arrs = [None] * 6 if rq is None else [getattr(rq, n) for n in names]
+        R = 0 if rq is None else arrs[0].numel()
+        P = 0 if rq is None else arrs[5].numel()
+        want = [(zone, torch.int32, H), (bw, torch.float64, Z * Z)]
+        if G:
+            want.append((group_anchor, torch.int32, G))
+        if rq is not None:
+            want += [(arrs[0], torch.int32, R), (arrs[1], torch.int32, R), (arrs[2], torch.int32, R),
+                     (arrs[3], torch.float64, R), (arrs[4], torch.int64, R + 1),
+                     (arrs[5], torch.float64, P)]
+        for t, dt, n in want:
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("rt_rows: a contiguous device tensor of %s with %d elements "
+                                 "expected" % (dt, n))
+        if H < 1 or Z < 1:
+            raise ValueError("rt_rows: at least one host and a (Z, Z) table")
+        if out is None:
+            out = torch.empty(rows * H, dtype=torch.float64, device=zone.device)
+        elif (out.dtype != torch.float64 or out.numel() < rows * H or not out.is_contiguous()
+              or not out.is_cuda):
+            raise ValueError("rt_rows: out must be a contiguous float64 device tensor with at "
+                             "least %d elements" % (rows * H))
+        q = _abi.pvt_route_queues()
+        q.n_hosts, q.n_zones, q.n_groups, q.n_routes = H, Z, G, R
+        q.zone, q.bw = zone.data_ptr(), bw.data_ptr()
+        q.group_anchor = group_anchor.data_ptr() if G else None
+        for f, t in zip(("rq_anchor", "rq_host", "rq_dir", "rq_bw", "rq_off", "rq_mbs"), arrs):
+            setattr(q, f, t.data_ptr() if t is not None and t.numel() else None)
+        q.n_packets, q.rt_bw = P, out.data_ptr()
+        self._bind_stream()
+        self._check(self.lib.pvt_rt_rows(self.ctx, ctypes.addressof(q)))
+        return out.view(-1)[:rows * H].view(rows, H)
 
     # -- metered resident cluster (pvt_host_meter_apply / _finish; reference
     #    resources/meter.py:59-81,181-187)

@@ -20,6 +20,11 @@ more kinds, ``CHECK_IN`` and ``CHECK_OUT``, whose amounts are ignored. ``apply_m
 those rules op by op on a ``HostMeterState``; ``ResidentCluster(..., meter=True)`` runs them on
 the device (``pvt_host_meter_apply`` / ``pvt_host_meter_finish``) and feeds the finished arrays
 to ``pvt_meter_usage`` and ``pvt_meter`` without a download.
+
+Realtime bandwidths (``scheduler/cost_aware.py:73-79``, ``resources/network.py:70-73``):
+``ResidentCluster.place(r, routes=rq)`` takes a ``routes.RouteQueues`` -- the routes that hold
+packets or have a bandwidth of their own -- instead of a dense ``r.rt_bw`` and builds the rows on
+the device (``pvt_rt_rows``); ``pivot_place/routes.py`` states that rule in plain Python.
 """
 import numpy as np
 
@@ -291,9 +296,10 @@ class ResidentCluster:
     and the hosts named by the logs applied since -- in one ``pvt_restore_hosts``.
 
     ``engine``: a ``PlacementEngine`` (or an object with its ``device``, ``host_ops``,
-    ``restore_hosts`` and ``run``). ``zone`` (H,), ``cost`` / ``bw`` (Z, Z) and the optional
-    ``tiebreak`` (H,) are the cluster's constants, uploaded once. ``bytes_uploaded`` counts every
-    host-to-device byte this object sends.
+    ``restore_hosts`` and ``run``; ``rt_rows`` as well for ``place(routes=...)``). ``zone``
+    (H,), ``cost`` / ``bw`` (Z, Z) and the optional ``tiebreak`` (H,) are the cluster's
+    constants, uploaded once. ``bytes_uploaded`` counts every host-to-device byte this object
+    sends.
 
     ``meter=True`` meters the cluster on the device as the reference's ``Meter`` does
     (``resources/meter.py:59-81,181-187``): ``apply`` then requires ``op_time`` and accepts
@@ -325,6 +331,7 @@ class ResidentCluster:
         if self.zone.numel() != self.n_hosts:
             raise ValueError("ResidentCluster: zone must name every host")
         self._stale = []        # device int32 tensors of hosts where work may differ from level
+        self._rt_rows = None    # place(routes=...): the rows built on the device (grows)
         self.meter = (DeviceMeter(torch, self.device, self.n_hosts, meter_log_capacity)
                       if meter else None)
 
@@ -409,12 +416,27 @@ class ResidentCluster:
         self.engine.restore_hosts(self.work, self.level, hosts)
         self._stale = []
 
-    def place(self, r: RoundArrays, want_avail=False) -> RoundResult:
+    def place(self, r: RoundArrays, want_avail=False, routes=None) -> RoundResult:
         """Place ``r``'s tasks on the resident state. ``r.avail`` is neither read nor uploaded,
         and ``r.zone``, ``r.cost``, ``r.bw`` and ``r.tiebreak`` give way to the cluster's own.
         The result's ``avail`` (the scratch after the policy's commits) is None unless
-        ``want_avail``."""
+        ``want_avail``.
+
+        ``routes``: a ``routes.RouteQueues`` of a cost_aware round with ``realtime_bw``, in place
+        of a dense ``r.rt_bw`` (passing both raises ValueError, and so does ``routes`` on another
+        policy). The list is uploaded -- its six arrays, counted in ``bytes_uploaded`` -- and the
+        rows of the round's anchors are built on the device (``pvt_rt_rows``) in a buffer the
+        cluster keeps and grows. First-fit without ``sort_hosts`` reads no route (reference
+        ``scheduler/cost_aware.py:118-119``): nothing is uploaded or built for it."""
         torch = self._torch
+        if routes is not None:
+            if r.rt_bw is not None:
+                raise ValueError("place: routes and r.rt_bw are two sources of the same rows")
+            if r.mode not in (_abi.PVT_CA_FF, _abi.PVT_CA_BF):
+                raise ValueError("place: routes belong to a cost_aware round, not to %s"
+                                 % _abi.MODE_NAMES.get(r.mode, r.mode))
+            if r.mode == _abi.PVT_CA_FF and not r.sort_hosts:
+                routes = None
         self.refresh()
         T = r.n_tasks
         dr = _ResidentRound()
@@ -430,12 +452,16 @@ class ResidentCluster:
         s.avail, s.zone = dr.avail.data_ptr(), dr.zone.data_ptr()
         s.cost, s.bw = dr.cost.data_ptr(), dr.bw.data_ptr()
         s.tiebreak = None if dr.tiebreak is None else dr.tiebreak.data_ptr()
-        keep = []
+        keep = {}
         for name in ("dem", "decay", "task_group", "group_anchor", "rt_bw"):
             a = getattr(r, name)
             t = None if a is None or a.size == 0 else self._up(np.ascontiguousarray(a).ravel())
-            keep.append(t)
+            keep[name] = t
             setattr(s, name, None if t is None else t.data_ptr())
+        if routes is not None:
+            # (rows per group only when the round has groups: pvt_round.rt_bw's convention)
+            anchors = keep["group_anchor"] if keep["task_group"] is not None else None
+            s.rt_bw = self._route_rows(routes, anchors).data_ptr()
         s.placement, s.order = dr.placement.data_ptr(), dr.order.data_ptr()
         s.mt_state = None if dr.mt is None else dr.mt.ctypes.data
         dr.struct = s
@@ -447,9 +473,24 @@ class ResidentCluster:
                                   if want_avail else None),
                            mt_state=dr.mt)
 
+    def _route_rows(self, routes, anchors):
+        """Upload ``routes`` and build the rows of ``anchors`` (a device tensor, or None for the
+        one row of zone 0) in the cluster's grow-only buffer; returns the rows."""
+        rq = _DeviceQueues()
+        for name, a in zip(("anchor", "host", "dir", "bw", "off", "mbs"), routes.arrays()):
+            setattr(rq, name, self._up(a))
+        need = (1 if anchors is None else anchors.numel()) * self.n_hosts
+        if self._rt_rows is None or self._rt_rows.numel() < need:
+            self._rt_rows = self._torch.empty(need, dtype=self._torch.float64, device=self.device)
+        return self.engine.rt_rows(self.zone, self.bw.view(-1), anchors, rq, out=self._rt_rows)
+
     def levels(self):
         """The true levels, (4, H) float64, downloaded."""
         return self.level.cpu().numpy().reshape(4, self.n_hosts).copy()
+
+
+class _DeviceQueues:
+    """The six arrays of a ``routes.RouteQueues`` as device tensors (``PlacementEngine.rt_rows``)."""
 
 
 class _ResidentRound:
